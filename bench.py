@@ -15,7 +15,11 @@ parameters (air/src/config.rs:54-67) and the Poseidon2 LMCS + challenger, the tr
           up on the node, the torch.distributed communicator is used; if no sharded proof can be made at all, the line
           falls back to N independent proofs and says so ("scaling": "weak", config.fallback).
 
-value = rows of the proved trace / seconds per step, whole job.  The CPU oracle is used ONLY for the `cpu_baseline` leg (a
+value = rows of the proved trace / seconds per step, whole job.  A plain run sets up, warms up, times the K steps and prints
+the line (`metric`, `value`, `unit`, `ms_per_step`, `config`, ...); `--dump-outputs DIR` also writes the proof of the last
+timed step as .npy files (see dump_outputs).  Everything else below is measured with `--full` only.
+
+With `--full`: the CPU oracle is used ONLY for the `cpu_baseline` leg (a
 bounded sample), never inside the timed GPU region.  Extra keys on the N = 1 line: `h2d_inclusive` (SURVEY.md section 8(d):
 the same proof with the host->device upload of the trace inside the timed region) and `miden_shape` (the full Miden VM
 shape: three AIRs of widths 51/22/16 with 4/3/1 EF aux columns, the published reference figure's neighbour) and `in_flight`
@@ -1018,6 +1022,26 @@ def hash_config_probe(pkg, device, log_n, lmcs, steps=5):
     return {"ms_per_proof": dt * 1e3, "rows_per_s": (1 << log_n) / dt, "proof_bytes": nbytes}
 
 
+def dump_outputs(proof, out_dir):
+    """What a caller of the timed path receives from one step -- the Proof of `prove` -- as DIR/<name>.npy in float64.  A Goldilocks
+    element (u64) does not fit a float64 mantissa, so every u64 becomes its two 32-bit halves on a last axis of 2: [low, high] (exact).
+    fields (F, 2), commitments (C, 4, 2), digest (4, 2), proof_bytes (B,) the serialised StarkProofData, log_trace_heights (T,).
+    A proof is a few hundred kB at most (logarithmic in the trace), far below the 64 MB bound."""
+    import numpy as np
+
+    def halves(a):
+        a = np.asarray(a, dtype=np.uint64)
+        return np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1).astype(np.float64)
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"fields": halves(proof.fields), "commitments": halves(proof.commitments), "digest": halves(proof.digest),
+              "proof_bytes": np.frombuffer(proof.bytes, dtype=np.uint8).astype(np.float64),
+              "log_trace_heights": np.asarray(proof.log_trace_heights, dtype=np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def cpu_baseline(runner, cpu_log_n):
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -1121,11 +1145,16 @@ def main():
     ap.add_argument("--shard-log-n", type=int, default=int(os.environ.get("MIDEN_BENCH_SHARD_LOG_N", "24")),
                     help="rows of the ONE proof sharded over the GPUs (N > 1)")
     ap.add_argument("--comm", default=os.environ.get("MIDEN_BENCH_COMM", "rccl"), choices=["rccl", "torch"])
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel breakdown, the rooflines, the H2D-inclusive figure, the real statement, the precompile session "
+                         "and the CPU baseline (the options below refine what --full measures); without it only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the proof of the last one as DIR/<name>.npy (float64; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="headline, roofline and CPU baseline only (no h2d_inclusive / real-statement probes)")
     ap.add_argument("--extras", action="store_true",
                     help="also the twenty side probes (miden_shape, jit_load, chiplets_air, the second client's per-chiplet sessions, in-flight "
-                         "proofs, the other hash configurations); the default line carries the headline, the H2D-inclusive figure, the real "
+                         "proofs, the other hash configurations); the --full line carries the headline, the H2D-inclusive figure, the real "
                          "statement under Poseidon2 and Blake3 and the whole precompile session")
     ap.add_argument("--cpu-log-n", type=int, default=18)
     args = ap.parse_args()
@@ -1247,13 +1276,15 @@ def main():
 
     for _ in range(args.warmup):
         runner.step()
-    # Timed region: HIP events around the DOMINANT kernel class only.  An event record is a barrier packet on the stream; with
-    # every class and span recorded (~130 scopes per proof) a 2^20-row proof is 0.5 ms slower (47.7 vs 47.2 ms).  The full
-    # per-class breakdown (`kernels`, `spans`, `sharded_breakdown`) comes from a second, untimed pass right after.
+    # Timed region.  With --full: HIP events around the DOMINANT kernel class only (for the rooflines).  An event record is a
+    # barrier packet on the stream; with every class and span recorded (~130 scopes per proof) a 2^20-row proof is 0.5 ms slower
+    # (47.7 vs 47.2 ms).  The full per-class breakdown (`kernels`, `spans`, `sharded_breakdown`) comes from a second, untimed pass
+    # right after.  A plain run records nothing.
     DOMINANT = "lmcs_leaf_absorb"
-    ctx.prof_filter(DOMINANT)
-    ctx.prof_enable(True)
-    ctx.prof_reset()
+    if args.full:
+        ctx.prof_filter(DOMINANT)
+        ctx.prof_enable(True)
+        ctx.prof_reset()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -1264,17 +1295,8 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    prof_timed = ctx.prof()
-    ctx.prof_filter(None)
-    ctx.prof_reset()
-    bd_steps = max(1, min(args.steps, 2 if mode == "sharded" else 5))
-    t_bd = time.perf_counter()
-    for _ in range(bd_steps):
-        runner.step()
-    barrier()
-    bd_ms = (time.perf_counter() - t_bd) / bd_steps * 1e3
-    prof = ctx.prof()
-    ctx.prof_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(runner.proof, args.dump_outputs)
 
     if mode == "sharded":
         how = {"rccl": "in-library RCCL collectives", "torch-nccl": "torch.distributed communicator, torch's RCCL",
@@ -1309,6 +1331,30 @@ def main():
         out["config"]["comm"] = {"chosen": comm_name, "mode": mode, "attempts": comm_log, "collective_timeout_s": float(os.environ.get("MH_COMM_TIMEOUT_S", "120")),
                                  "note": "rank 0's view; every attempt runs on a watchdog thread (MIDEN_BENCH_COMM_TIMEOUT) and the ranks agree on its outcome "
                                          "over the gloo control plane; inside the library every collective is bounded by MH_COMM_TIMEOUT_S (error code, no hang)"}
+
+    def shutdown():
+        if comm is not None and hasattr(comm, "close"):
+            comm.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        shutdown()
+        return
+
+    prof_timed = ctx.prof()
+    ctx.prof_filter(None)
+    ctx.prof_reset()
+    bd_steps = max(1, min(args.steps, 2 if mode == "sharded" else 5))
+    t_bd = time.perf_counter()
+    for _ in range(bd_steps):
+        runner.step()
+    barrier()
+    bd_ms = (time.perf_counter() - t_bd) / bd_steps * 1e3
+    prof = ctx.prof()
+    ctx.prof_enable(False)
     if mode == "sharded":
         # the measured split of this rank's time next to the model of DESIGN.md section 5 (miden-vm_amd/sharding.py), so that the
         # line can be read against a prediction: sharded kernels, the replicated inverse transforms, collectives
@@ -1527,10 +1573,7 @@ def main():
         bulky = [k for k in out if k not in first and k not in last]
         out = {**{k: out[k] for k in first if k in out}, **{k: out[k] for k in bulky}, **{k: out[k] for k in last if k in out}, "summary": summary}
         print(json.dumps(out), flush=True)
-    if comm is not None and hasattr(comm, "close"):
-        comm.close()
-    if world > 1:
-        dist.destroy_process_group()
+    shutdown()
 
 
 if __name__ == "__main__":

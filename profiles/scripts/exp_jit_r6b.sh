@@ -12,5 +12,5 @@ run MH_JIT_MAXREGS=168
 unset MH_JIT_CACHE_DIR
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu_b.txt 2>&1
 tail -5 $O/pytest_gpu_b.txt
-timeout 900 python bench.py > $O/bench_default_b.json 2> $O/bench_default_b.err
+timeout 900 python bench.py --full > $O/bench_default_b.json 2> $O/bench_default_b.err
 tail -c 3000 $O/bench_default_b.json

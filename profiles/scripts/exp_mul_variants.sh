@@ -8,7 +8,7 @@ grep -E "variant|permute|S-box|serial|mismatch" gpurun_out/r2/permbench2.txt | a
 for lib in "" exp/libnttasm.so exp/libc.so; do
   if [ -n "$lib" ]; then export MIDENHIP_LIB=$PWD/miden-vm_amd/lib/$lib; else unset MIDENHIP_LIB; fi
   echo "== lib: ${lib:-default}"
-  timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "
+  timeout 300 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 print('ms_per_step %.2f' % d['ms_per_step'], {k: round(v['ms_per_step'],2) for k,v in d['kernels'].items()})"

@@ -20,5 +20,5 @@ print("2p16", {k: (round(v, 2) if isinstance(v, float) else v) for k, v in d.ite
 PY
 timeout 2700 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.txt 2>&1
 tail -4 $O/pytest_gpu.txt
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -c 1800 $O/bench_default.json

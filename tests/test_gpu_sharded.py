@@ -578,12 +578,12 @@ def test_the_bench_launcher_path_at_two_ranks_on_one_device(tmp_path):
     N = 2 on the one device of the test box: rendezvous on 127.0.0.1, the communicator ladder (RCCL refuses two ranks on one device, so the
     first rung must FAIL with an error on the line, not hang, and the ladder must land on the torch communicator), the 2^12 trial proof, one
     proof sharded over both ranks, the real statement sharded (a short program), and the one JSON line with `config.comm`, `scale_note` and
-    the summary last."""
+    the summary last.  Run with `--full`: the real statement, the breakdown and the summary are measured only there."""
     import json, subprocess
     env = dict(os.environ, MIDEN_BENCH_COMM_TIMEOUT="90", MH_COMM_TIMEOUT_S="60", MIDEN_BENCH_REAL_ITERS="60", HSA_ENABLE_IPC_MODE_LEGACY="0")
     port = 29500 + (os.getpid() + 1777) % 2000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--shard-log-n", "14"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--shard-log-n", "14", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]

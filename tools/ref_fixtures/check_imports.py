@@ -290,6 +290,39 @@ class Workspace:
                     return [a for a in split_args(body[:close_paren(body)]) if not re.match(r"^(&\s*)?(mut\s+)?self\b", a)]
         return None
 
+    def workspace_dependency(self, name):
+        """`name = ...` in the checkout's root Cargo.toml ([workspace.dependencies])."""
+        return re.search(r"^" + re.escape(name) + r"\s*=", open(os.path.join(self.ref, "Cargo.toml")).read(), re.M) is not None
+
+    def crate_feature(self, crate, feat):
+        d = self.crates.get(crate.replace("-", "_"))
+        return bool(d) and re.search(r"^" + feat + r"\s*=", open(os.path.join(d[1], "Cargo.toml")).read(), re.M) is not None
+
+    def precedent(self, pat):
+        """Does the pattern occur anywhere in the checkout's sources?"""
+        return any(re.search(pat, c) for c in self.sources().values())
+
+    def config_fn_arity(self, fn_name):
+        """Number of parameters of `pub fn fn_name` in air/src/config.rs, None if there is none."""
+        cfg_src = self.sources().get(os.path.join("air", "src", "config.rs"), "")
+        m = re.search(r"\bpub\s+fn\s+" + fn_name + r"\b\s*(?:<[^(]*>)?\s*\(", cfg_src)
+        return len(split_args(cfg_src[m.end():][:close_paren(cfg_src[m.end():])])) if m else None
+
+    def has_method(self, type_name, method):
+        return self.find_method(type_name, method) is not None
+
+    def has_field(self, struct, field):
+        return self.find_field(struct, field) is not None
+
+    def signature(self, type_name, method, fragments):
+        """The declaration of Type::method against the kits' assumption: None if not found, else {"params": number of parameters,
+        "mentions": [does parameter i mention fragments[i]] (an empty fragment: True)}."""
+        params = self.method_params(type_name, method)
+        if params is None:
+            return None
+        return {"params": len(params),
+                "mentions": [not frag or frag.replace(" ", "") in prm.replace(" ", "") for prm, frag in zip(params, fragments)]}
+
     def find_field(self, struct, field):
         pat = re.compile(r"\bstruct\s+" + re.escape(struct) + r"\b[^{;]*\{")
         want = re.compile(r"\bpub\s+" + re.escape(field) + r"\s*:")
@@ -305,6 +338,66 @@ class Workspace:
                 if want.search(s[m.end():i]):
                     return rel
         return None
+
+
+# Everything check() asks of the reference, by query kind: a Workspace answers from a checkout, RecordedWorkspace from the answers
+# a checkout once gave (tests/golden/rust_kit_facts.json, written by tests/golden/make_rust_kit_facts.py through RecordingWorkspace).
+# Every answer is a verdict (a bool, a count, "ok" / "external" / None), never text of the checkout.
+QUERIES = ("workspace_dependency", "crate_feature", "resolve", "has_method", "precedent", "signature", "config_fn_arity", "has_field")
+
+
+def fact_key(kind, args):
+    return kind + " " + " ".join("::".join(a) if isinstance(a, (list, tuple)) else str(a) for a in args)
+
+
+class RecordingWorkspace:
+    """A Workspace that notes every answer it gives in `facts` ({fact_key: answer})."""
+
+    def __init__(self, ws):
+        self.ws, self.facts = ws, {}
+
+    def __getattr__(self, kind):
+        if kind not in QUERIES:
+            raise AttributeError(kind)
+
+        def ask(*args):
+            ans = getattr(self.ws, kind)(*args)
+            self.facts[fact_key(kind, args)] = ans
+            return ans
+        return ask
+
+
+class RecordedWorkspace:
+    """The recorded answers of a checkout, replayed without it.  A query they do not hold raises: the kits ask something new."""
+
+    def __init__(self, facts):
+        self.facts = facts
+
+    def __getattr__(self, kind):
+        if kind not in QUERIES:
+            raise AttributeError(kind)
+
+        def ask(*args):
+            key = fact_key(kind, args)
+            if key not in self.facts:
+                raise KeyError(f"`{key}` is not among the recorded answers of the reference: re-record them with "
+                               "tests/golden/make_rust_kit_facts.py <miden-vm checkout>")
+            return self.facts[key]
+        return ask
+
+
+# Queries with a known answer in the reference: the resolver's own check (tests/test_rust_kit_imports.py).
+RESOLVER_PROBES = [
+    ("resolve", (["miden_crypto", "stark", "ProverInstance"],), "ok"),            # inline mod + pub use of another crate
+    ("resolve", (["miden_crypto", "stark", "proof", "StarkProofData"],), "ok"),   # re-exported sub-module
+    ("resolve", (["miden_air", "config", "poseidon2_config"],), "ok"),
+    ("resolve", (["miden_lifted_stark", "testing", "airs", "miden", "DummyMidenAir"],), "ok"),
+    ("resolve", (["miden_crypto", "stark", "air", "symbolic", "SymbolicAirBuilder"],), "external"),  # glob of p3-air: unverifiable
+    ("resolve", (["miden_crypto", "stark", "air", "BasedVectorSpace"],), None),   # the wrong path the kits used to import
+    ("resolve", (["miden_crypto", "stark", "NoSuchThing"],), None),
+    ("has_method", ("ProverInstance", "prove"), True), ("has_method", ("ProverInstance", "no_such_method"), False),
+    ("has_field", ("StarkProof", "quotient_commit"), True), ("has_field", ("StarkProof", "no_such_field"), False),
+]
 
 
 def close_paren(s):
@@ -412,24 +505,23 @@ PRECEDENTS = [
 
 
 def check(ref, kit_dir):
-    ws = Workspace(ref)
+    """ref: a checkout's path, or an object answering QUERIES (RecordedWorkspace, RecordingWorkspace)."""
+    ws = Workspace(ref) if isinstance(ref, str) else ref
     problems, report = [], []
     # Cargo.toml: every dependency is a workspace dependency that exists
     cargo = open(os.path.join(kit_dir, "Cargo.toml")).read()
-    root_cargo = open(os.path.join(ref, "Cargo.toml")).read()
     deps = re.search(r"^\[dependencies\](.*?)^\[", cargo, re.S | re.M).group(1)
     for name in re.findall(r"^([\w-]+)\s*=", deps, re.M):
-        in_ws = re.search(r"^" + re.escape(name) + r"\s*=", root_cargo, re.M) is not None
+        in_ws = ws.workspace_dependency(name)
         report.append(("dependency", name, "workspace" if in_ws else "MISSING"))
         if not in_ws:
             problems.append(f"Cargo.toml: `{name}` is not a [workspace.dependencies] entry of the reference")
     for feat_crate, feat in re.findall(r'"([\w-]+)/(\w+)"', cargo):
-        d = ws.crates.get(feat_crate.replace("-", "_"))
-        if not d or not re.search(r"^" + feat + r"\s*=", open(os.path.join(d[1], "Cargo.toml")).read(), re.M):
+        if not ws.crate_feature(feat_crate, feat):
             problems.append(f"Cargo.toml: feature `{feat_crate}/{feat}` does not exist")
     m = re.search(r'miden-lifted-stark\s*=\s*\{[^}]*features\s*=\s*\[([^\]]*)\]', cargo)
     for feat in re.findall(r'"(\w+)"', m.group(1)) if m else []:
-        if not re.search(r"^" + feat + r"\s*=", open(os.path.join(ws.crates["miden_lifted_stark"][1], "Cargo.toml")).read(), re.M):
+        if not ws.crate_feature("miden-lifted-stark", feat):
             problems.append(f"Cargo.toml: miden-lifted-stark has no feature `{feat}`")
     files = [os.path.join(kit_dir, "src", "main.rs")] + sorted(
         os.path.join(kit_dir, "src", "bin", f) for f in os.listdir(os.path.join(kit_dir, "src", "bin")) if f.endswith(".rs"))
@@ -445,53 +537,50 @@ def check(ref, kit_dir):
         if r != "ok":
             problems.append(f"miden_air::config::{item} not found")
     for t, meth in METHODS:
-        where = ws.find_method(t, meth)
-        report.append(("method", f"{t}::{meth}", where or "NOT FOUND"))
-        if not where:
+        found = ws.has_method(t, meth)
+        report.append(("method", f"{t}::{meth}", "found" if found else "NOT FOUND"))
+        if not found:
             problems.append(f"no `fn {meth}` in an impl / trait block of `{t}`")
-    corpus = list(ws.sources().values())
     kit_src = "".join(strip_source(open(f).read()) for f in files)
     for pat in PRECEDENTS:
         used = re.search(pat, kit_src) is not None
-        found = any(re.search(pat, c) for c in corpus)
+        found = ws.precedent(pat)
         report.append(("precedent", pat, ("in reference" if found else "NOT IN REFERENCE") + ("" if used else " (unused by the kits)")))
         if used and not found:
             problems.append(f"external API pattern /{pat}/ is used by the kits but nowhere in the reference")
     for t, meth, want in SIGNATURES:
-        params = ws.method_params(t, meth)
-        report.append(("signature", f"{t}::{meth}", "(" + ", ".join(params or []) + ")" if params is not None else "NOT FOUND"))
-        if params is None:
+        sig = ws.signature(t, meth, want)
+        report.append(("signature", f"{t}::{meth}", f"{sig['params']} parameter(s)" if sig is not None else "NOT FOUND"))
+        if sig is None:
             problems.append(f"cannot find the declaration of {t}::{meth}")
             continue
-        if len(params) != len(want):
-            problems.append(f"{t}::{meth} takes {len(params)} parameter(s) in the reference, the kits assume {len(want)}: {params}")
-        for prm, frag in zip(params, want):
-            if frag and frag.replace(" ", "") not in prm.replace(" ", ""):
-                problems.append(f"{t}::{meth}: parameter `{prm}` does not mention `{frag}`")
+        if sig["params"] != len(want):
+            problems.append(f"{t}::{meth} takes {sig['params']} parameter(s) in the reference, the kits assume {len(want)}")
+        for i, (ok, frag) in enumerate(zip(sig["mentions"], want)):
+            if not ok:
+                problems.append(f"{t}::{meth}: parameter {i} does not mention `{frag}`")
         calls = [args for ufcs, args in kit_calls(kit_src, t, meth) if ufcs] or \
                 ([args for ufcs, args in kit_calls(kit_src, t, meth)] if meth not in ("new",) else [])
         for args in calls:
             if len(args) != len(want):
                 problems.append(f"a kit calls {t}::{meth} with {len(args)} argument(s) {args}, the reference declares {len(params)}")
         report.append(("call sites", f"{t}::{meth}", str(len(calls))))
-    cfg_src = ws.sources().get(os.path.join("air", "src", "config.rs"), "")
     for fn_name, n in CONFIG_SIGNATURES.items():
-        m = re.search(r"\bpub\s+fn\s+" + fn_name + r"\b\s*(?:<[^(]*>)?\s*\(", cfg_src)
-        if not m:
+        arity = ws.config_fn_arity(fn_name)
+        if arity is None:
             problems.append(f"air/src/config.rs has no `pub fn {fn_name}`")
             continue
-        params = split_args(cfg_src[m.end():][:close_paren(cfg_src[m.end():])])
-        report.append(("signature", f"config::{fn_name}", "(" + ", ".join(params) + ")"))
-        if len(params) != n:
-            problems.append(f"config::{fn_name} takes {len(params)} parameter(s), the kits assume {n}")
+        report.append(("signature", f"config::{fn_name}", f"{arity} parameter(s)"))
+        if arity != n:
+            problems.append(f"config::{fn_name} takes {arity} parameter(s), the kits assume {n}")
         for mm in re.finditer(r"config::" + fn_name + r"\s*\(", kit_src):
             args = split_args(kit_src[mm.end():][:close_paren(kit_src[mm.end():])])
             if len(args) != n:
                 problems.append(f"a kit calls config::{fn_name} with {len(args)} argument(s)")
     for s, fld in FIELDS:
-        where = ws.find_field(s, fld)
-        report.append(("field", f"{s}.{fld}", where or "NOT FOUND"))
-        if not where:
+        found = ws.has_field(s, fld)
+        report.append(("field", f"{s}.{fld}", "found" if found else "NOT FOUND"))
+        if not found:
             problems.append(f"struct `{s}` has no public field `{fld}`")
     return problems, report
 

@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 O = os.path.join(ROOT, "gpurun_out", "final")
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02_final"
 out = []
-out.append("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras   (7 proofs of miden:20:51:8: 1 warm-up, 3 timed, 3 of the breakdown pass; ns)")
+out.append("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras   (7 proofs of miden:20:51:8: 1 warm-up, 3 timed, 3 of the breakdown pass; ns)")
 out.append("# (k_perm_rate = the register-only Poseidon2 rate bench.py reports next to roofline_valu; it runs once, outside the timed region)")
 out.append(open(os.path.join(O, "kt", "kt_kernel_stats.csv")).read().strip())
 
@@ -43,7 +43,7 @@ if la_sq:
     out.append(f"# k_leaf_absorb: SQ_INSTS_VALU per permutation = {la_sq['SQ_INSTS_VALU'] * 64 / perms:.0f} wave-instructions x 64 lanes / {perms} permutations "
                f"= {la_sq['SQ_INSTS_VALU'] / (perms / 64):.0f} VALU instructions per permutation (loads/stores and address arithmetic of the kernel included)")
 bench = open(os.path.join(O, "bench.json")).read().strip().splitlines()[-1]
-out.append("# bench line (same build, un-profiled, python bench.py --steps 20 --warmup 5):")
+out.append("# bench line (same build, un-profiled, python bench.py --steps 20 --warmup 5 --full):")
 out.append(bench)
 open(os.path.join(ROOT, "profiles", f"{tag}_rocprof.txt"), "w").write("\n".join(out) + "\n")
 la = per_launch.get("k_leaf_absorb", {})
