@@ -14,6 +14,21 @@ pub const MH_ERR_HIP: c_int = 2;
 pub const MH_ERR_OOM: c_int = 3;
 pub const MH_ERR_INTERNAL: c_int = 4;
 pub const MH_ERR_COMM: c_int = 5;
+/// mh_check_*: the trace does not satisfy the statement; the entries say where.
+pub const MH_ERR_UNSATISFIED: c_int = 6;
+/// mh_check_* flags: evaluate every constraint on every row (no fold screen).
+pub const MH_CHECK_EXACT: c_int = 1;
+
+/// One failing constraint (or external assertion, instance = -1) of a constraint check.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_check_entry {
+    pub instance: i32,
+    pub constraint: u32,
+    pub rows: u64,
+    pub first_row: u64,
+    pub value: [u64; 2],
+}
 
 /// PcsParams (crates/lifted-stark/src/pcs/params.rs:52-96).
 #[repr(C)]
@@ -202,4 +217,10 @@ unsafe extern "C" {
     pub fn mh_proof_num_traces(p: *const mh_proof) -> usize;
     pub fn mh_proof_log_trace_heights(p: *const mh_proof) -> *const u8;
     pub fn mh_proof_serialize(p: *const mh_proof, out: *mut u8, cap: usize) -> usize;
+    // ---- constraint checker (ExecutionTrace::check_constraints, SessionTraces::check): MH_OK or MH_ERR_UNSATISFIED + the entries
+    pub fn mh_check_constraints(ctx: *mut mh_ctx, air: *const mh_air, main_trace: *const mh_trace, aux: *const mh_trace, preprocessed: *const mh_trace, public_values: *const u64, n_public: usize, randomness: *const u64, n_randomness: usize, aux_values: *const u64, n_aux_values: usize, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize, failing_rows: *mut u64) -> c_int;
+    pub fn mh_check_miden(ctx: *mut mh_ctx, m: *const mh_miden, core_rowmajor: *const u64, log_core: c_int, chiplets_rowmajor: *const u64, log_chiplets: c_int, poseidon2_rowmajor: *const u64, log_poseidon2: c_int, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize) -> c_int;
+    pub fn mh_check_miden_traces(ctx: *mut mh_ctx, m: *const mh_miden, traces: *const *mut mh_trace, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize) -> c_int;
+    pub fn mh_check_precompile(ctx: *mut mh_ctx, s: *mut mh_precompile, mains_rowmajor: *const *const u64, log_heights: *const c_int, public_root: *const u64, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize) -> c_int;
+    pub fn mh_check_precompile_traces(ctx: *mut mh_ctx, s: *mut mh_precompile, traces: *const *mut mh_trace, public_root: *const u64, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize) -> c_int;
 }

@@ -524,6 +524,49 @@ size_t mh_proof_serialize(const mh_proof* p, uint8_t* out, size_t cap);
  * StarkProofData and comes back zeroed (mh_verify recomputes it). */
 int mh_proof_deserialize(const uint8_t* bytes, size_t len, mh_proof** out);
 
+/* ---- constraint checker: ExecutionTrace::check_constraints / SessionTraces::check (crates/lifted-stark/src/debug.rs) ---------------
+ * Evaluates every constraint of an AIR on every row of a trace, on the device, and reports which constraints fail where -- a debugging
+ * tool for witness generators, not part of any proof (no Fiat-Shamir transcript; the statement entries derive debug challenges).
+ * Two stages (csrc/check.hip): the screen folds every constraint with a fresh random alpha per call and flags the rows where the fold does
+ * not vanish (a failing row escapes with probability <= K / p^2); the exact stage then evaluates each constraint on those rows with the
+ * reference's debug selectors (is_first = [r == 0], is_last = [r == n-1], is_transition = [r != n-1], next row = (r + 1) mod n).
+ * MH_CHECK_EXACT skips the screen and evaluates every constraint on every row.
+ * MH_OK: every constraint and every external assertion vanishes.  MH_ERR_UNSATISFIED: they do not; mh_last_error names the first entry.
+ * *n_entries = the number of entries, even when it exceeds cap; the first cap are written, ordered by (instance, first_row,
+ * constraint), external assertions last. */
+#define MH_ERR_UNSATISFIED 6 /* mh_check_*: the trace does not satisfy the statement; the entries say where */
+#define MH_CHECK_EXACT 1     /* flags: evaluate every constraint on every row (no fold screen) */
+typedef struct mh_check_entry {
+  int32_t instance;    /* AIR instance in the statement's instance order; -1: an external (cross-AIR) assertion */
+  uint32_t constraint; /* constraint index in the DAG (= the reference's emission order); external: assertion index */
+  uint64_t rows;       /* rows on which it does not vanish (external: 1) */
+  uint64_t first_row;  /* the smallest such row (external: 0) */
+  uint64_t value[2];   /* its value there, EF (c1 = 0 for a base-field constraint) */
+} mh_check_entry;
+/* One AIR over one trace (instance 0 in the entries).  aux: the aux trace (2 * aux_width base columns, as mh_lookup_build_aux makes it),
+ * required when the AIR has aux columns; preprocessed: the raw preprocessed matrix, or NULL for the one attached to the AIR.
+ * randomness / aux_values: EF pairs, at least as many as the AIR reads.  failing_rows: NULL, or room for 2^log_n + 1 words:
+ * [0] = the number m of rows on which some constraint fails, [1..m] = those rows, ascending. */
+int mh_check_constraints(mh_ctx* ctx, const mh_air* air, const mh_trace* main_trace, const mh_trace* aux /* or NULL */,
+                         const mh_trace* preprocessed /* or NULL */, const uint64_t* public_values, size_t n_public,
+                         const uint64_t* randomness /* EF pairs */, size_t n_randomness, const uint64_t* aux_values /* EF pairs */,
+                         size_t n_aux_values, int flags, mh_check_entry* out, size_t cap, size_t* n_entries, uint64_t* failing_rows);
+/* The statements: the arguments of the provers without hash_fn.  Aux columns are built on the device by the attached lookup programs with
+ * debug challenges: a Poseidon2 duplex challenger started from the statement's challenger state observes the pre-observe schedule
+ * (mh_miden_pre_observe; mh_precompile_pre_observe with 0^4 for the preprocessed commitment), the number of AIRs and their log heights
+ * in instance order, then samples the lookup challenges -- the transcript order of a proof up to the main commitment, which it omits.
+ * Then the statement's eval_external and every instance are checked. */
+int mh_check_miden(mh_ctx* ctx, const mh_miden* m, const uint64_t* core_rowmajor, int log_core, const uint64_t* chiplets_rowmajor,
+                   int log_chiplets, const uint64_t* poseidon2_rowmajor, int log_poseidon2, const uint64_t* public_values /* [32] */,
+                   const uint64_t* aux_inputs, size_t n_aux_inputs, int flags, mh_check_entry* out, size_t cap, size_t* n_entries);
+int mh_check_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* const traces[3], const uint64_t* public_values,
+                          const uint64_t* aux_inputs, size_t n_aux_inputs, int flags, mh_check_entry* out, size_t cap, size_t* n_entries);
+int mh_check_precompile(mh_ctx* ctx, mh_precompile* s, const uint64_t* const mains_rowmajor[MH_PRECOMPILE_NUM_AIRS],
+                        const int log_heights[MH_PRECOMPILE_NUM_AIRS], const uint64_t public_root[4], int flags, mh_check_entry* out,
+                        size_t cap, size_t* n_entries);
+int mh_check_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_trace* const traces[MH_PRECOMPILE_NUM_AIRS], const uint64_t public_root[4],
+                               int flags, mh_check_entry* out, size_t cap, size_t* n_entries);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ EXPORTS = [
     "mh_local_fabric_create", "mh_local_fabric_destroy", "mh_local_fabric_abort", "mh_comm_create_local",
     "mh_miden_load", "mh_miden_free", "mh_prove_miden", "mh_prove_miden_traces", "mh_verify_miden", "mh_miden_pcs_params",
     "mh_miden_challenger_state", "mh_miden_hash_kernel_digests", "mh_miden_pre_observe", "mh_miden_eval_external", "mh_miden_air_blob",
+    "mh_check_constraints", "mh_check_miden", "mh_check_miden_traces", "mh_check_precompile", "mh_check_precompile_traces",
 ]
 
 # the in-tree cache of precompiled constraint kernels (filled by __graft_entry__.build() / tools/jit_precompile.py); $MH_JIT_CACHE_DIR wins
@@ -51,6 +52,43 @@ _lib = None
 
 class MidenHipError(RuntimeError):
     pass
+
+
+# ---- constraint checker (include/midenhip.h mh_check_*) ----
+MH_ERR_UNSATISFIED = 6  # the trace does not satisfy the statement; the entries say where
+MH_CHECK_EXACT = 1      # flags: evaluate every constraint on every row (no fold screen)
+
+
+class CheckEntry(C.Structure):
+    """mh_check_entry: a constraint of `instance` that does not vanish on `rows` rows, the first being `first_row` where it takes
+    `value` (EF pair); instance -1 is an external (cross-AIR) assertion, `constraint` its index."""
+    _fields_ = [("instance", C.c_int32), ("constraint", C.c_uint32), ("rows", C.c_uint64), ("first_row", C.c_uint64),
+                ("value", C.c_uint64 * 2)]
+
+    def key(self):
+        return (self.instance, self.constraint, self.rows, self.first_row, self.value[0], self.value[1])
+
+    def __eq__(self, other):
+        return isinstance(other, CheckEntry) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return (f"CheckEntry(instance={self.instance}, constraint={self.constraint}, rows={self.rows}, first_row={self.first_row}, "
+                f"value=({self.value[0]}, {self.value[1]}))")
+
+
+def _run_check(ctx, call, cap=256):
+    """call(out, cap, n_ptr) -> rc; re-run with room for every entry when the first buffer was short."""
+    while True:
+        out, n = (CheckEntry * max(1, cap))(), C.c_size_t(0)
+        rc = call(out, C.c_size_t(cap), C.byref(n))
+        if rc not in (0, MH_ERR_UNSATISFIED):
+            ctx.check(rc)
+        if n.value <= cap:
+            return [out[i] for i in range(n.value)]
+        cap = n.value
 
 
 def load_library():
@@ -422,6 +460,32 @@ class DeviceAir:
             pass
 
 
+def _as_trace(ctx, m):
+    return m if m is None or isinstance(m, Trace) else Trace(ctx, m)
+
+
+def check_constraints(ctx, dev_air, main, aux=None, preprocessed=None, publics=(), randomness=(), aux_values=(), exact=False):
+    """mh_check_constraints: every constraint of `dev_air` (a DeviceAir) on every row of `main` (a Trace or a host matrix).
+    aux: the aux trace (2 * aux_width base columns, as DeviceLookup.build_aux makes it); randomness / aux_values: EF pairs.
+    -> (entries, failing_rows): the failing constraints (list of CheckEntry, [] when satisfied) and the ascending rows on which any
+    constraint fails.  exact=True evaluates every constraint on every row instead of screening the rows with a random fold."""
+    lib = ctx.lib
+    main, aux, preprocessed = _as_trace(ctx, main), _as_trace(ctx, aux), _as_trace(ctx, preprocessed)
+    pub = _arr([int(x) for x in publics] or [0])
+    rnd = _arr([int(x) for r in randomness for x in r] or [0])
+    av = _arr([int(x) for r in aux_values for x in r] or [0])
+    rows = np.zeros((1 << main.log_n) + 1, dtype=np.uint64)
+
+    def call(out, cap, n):
+        return lib.mh_check_constraints(ctx.h, dev_air.h, main.h, aux.h if aux is not None else None,
+                                        preprocessed.h if preprocessed is not None else None, _ptr(pub), C.c_size_t(len(publics)),
+                                        _ptr(rnd), C.c_size_t(len(randomness)), _ptr(av), C.c_size_t(len(aux_values)),
+                                        C.c_int(MH_CHECK_EXACT if exact else 0), out, cap, n, _ptr(rows))
+
+    entries = _run_check(ctx, call)
+    return entries, [int(x) for x in rows[1:1 + int(rows[0])]]
+
+
 class DeviceLookup:
     """mh_lookup: a LogUp lookup program ("MHLKP001" blob, dag.LookupBuilder) compiled for the device."""
 
@@ -755,6 +819,26 @@ class Miden:
         self.ctx.check(rc)
         return Proof(lib, out)
 
+    def check(self, core, chiplets, poseidon2, public_values, aux_inputs, exact=False):
+        """mh_check_miden(_traces): ExecutionTrace::check_constraints of this statement -> [CheckEntry] ([] when every constraint and the
+        bus balance hold); host row-major matrices or Trace objects.  An unsatisfied statement is a result, not an error."""
+        lib, mats = self.ctx.lib, (core, chiplets, poseidon2)
+        pv, aux = _arr([int(x) for x in public_values]), _arr([int(x) for x in aux_inputs] or [0])
+        flags = C.c_int(MH_CHECK_EXACT if exact else 0)
+        if all(isinstance(m, Trace) for m in mats):
+            tr = (C.c_void_p * 3)(*[m.h for m in mats])
+            call = lambda out, cap, n: lib.mh_check_miden_traces(self.ctx.h, self.h, tr, _ptr(pv), _ptr(aux), C.c_size_t(len(aux_inputs)),
+                                                                 flags, out, cap, n)
+        else:
+            hs = [np.ascontiguousarray(m, dtype=np.uint64) for m in mats]
+            lg = [int(m.shape[0]).bit_length() - 1 for m in hs]
+            if [m.shape[1] for m in hs] != [51, 22, 16] or any(m.shape[0] != 1 << l for m, l in zip(hs, lg)):
+                raise MidenHipError("Miden.check: widths 51 / 22 / 16 and power-of-two heights expected")
+            call = lambda out, cap, n: lib.mh_check_miden(self.ctx.h, self.h, _ptr(hs[0]), C.c_int(lg[0]), _ptr(hs[1]), C.c_int(lg[1]),
+                                                          _ptr(hs[2]), C.c_int(lg[2]), _ptr(pv), _ptr(aux), C.c_size_t(len(aux_inputs)),
+                                                          flags, out, cap, n)
+        return _run_check(self.ctx, call)
+
     def free(self):
         if getattr(self, "h", None) and self.ctx.h:
             self.ctx.lib.mh_miden_free(self.h)
@@ -814,6 +898,26 @@ class Precompile:
             rc = lib.mh_prove_precompile(self.ctx.h, self.h, C.c_int(Ctx.LMCS[hash_fn]), ptrs, (C.c_int * 12)(*lg), _ptr(root), C.byref(out))
         self.ctx.check(rc)
         return Proof(lib, out)
+
+    def check(self, mains, public_root, exact=False):
+        """mh_check_precompile(_traces): SessionTraces::check -> [CheckEntry] ([] when the session is satisfied)."""
+        lib = self.ctx.lib
+        if len(mains) != 12:
+            raise MidenHipError("Precompile.check: twelve main traces expected")
+        root = _arr([int(x) for x in public_root])
+        flags = C.c_int(MH_CHECK_EXACT if exact else 0)
+        if all(isinstance(m, Trace) for m in mains):
+            tr = (C.c_void_p * 12)(*[m.h for m in mains])
+            call = lambda out, cap, n: lib.mh_check_precompile_traces(self.ctx.h, self.h, tr, _ptr(root), flags, out, cap, n)
+        else:
+            hs = [np.ascontiguousarray(m, dtype=np.uint64) for m in mains]
+            lg = [int(m.shape[0]).bit_length() - 1 for m in hs]
+            if tuple(m.shape[1] for m in hs) != self.WIDTHS or any(m.shape[0] != 1 << l for m, l in zip(hs, lg)):
+                raise MidenHipError("Precompile.check: the AIRs' widths and power-of-two heights expected")
+            ptrs = (u64p * 12)(*[_ptr(m) for m in hs])
+            lh = (C.c_int * 12)(*lg)
+            call = lambda out, cap, n: lib.mh_check_precompile(self.ctx.h, self.h, ptrs, lh, _ptr(root), flags, out, cap, n)
+        return _run_check(self.ctx, call)
 
     def free(self):
         if getattr(self, "h", None) and self.ctx.h:

@@ -1,5 +1,6 @@
 // Internal interfaces between the translation units of libmidenhip (not part of the C ABI).
 #pragma once
+#include "../../include/midenhip.h"
 #include "ctx.hpp"
 #include <vector>
 
@@ -175,3 +176,14 @@ u64 fri_grind_bytes(mh_ctx* c, int lmcs, const std::vector<uint8_t>& prefix, int
 struct mh_lookup;
 mh_trace* lookup_build_aux(mh_ctx* c, const mh_lookup* lk, const mh_trace* main, const mh_trace* prep, const std::vector<e2>& randomness,
                            e2* acc_final);
+
+// quotient.hip: the screen of the constraint checker -- the AIR's constraint program on the trace domain, alpha-folded into acc [2][n]
+void constraint_fold_trace_domain(mh_ctx* c, const mh_air* air, const mh_trace* main, const mh_trace* aux, const mh_trace* prep,
+                                  const u64* inv_first, const u64* inv_last, const std::vector<u64>& publics, const std::vector<e2>& randomness,
+                                  const std::vector<e2>& aux_values, e2 alpha, u64* acc);
+// check.hip: the checker of one statement (mh_check_miden*, mh_check_precompile*): debug challenges from the statement's challenger state
+// and pre-observe schedule, aux traces by the attached lookup programs, every instance, then `ext`.  preps: per instance the raw
+// preprocessed matrix, or null (the AIR's own).  names: per instance, for mh_last_error.  Never throws.
+int check_statement(mh_ctx* c, int n_airs, mh_air* const* airs, mh_trace* const* traces, const mh_trace* const* preps, const u64* publics,
+                    size_t n_publics, const u64 challenger_state[12], const u64* pre_observe, size_t n_pre, mh_external_assertions ext,
+                    void* ext_user, const char* const* names, int flags, mh_check_entry* out, size_t cap, size_t* n_entries);

@@ -18,6 +18,8 @@
 #include "../../include/midenhip.h"
 #include "ctx.hpp"
 #include "gl.cuh"
+#include "air.hpp"
+#include "kernels.hpp"
 #include "poseidon2.cuh"
 #include <cstring>
 #include <memory>
@@ -285,6 +287,51 @@ int mh_verify_miden(int hash_fn, const uint64_t* public_values, const uint64_t* 
   return mh_verify_lmcs(hash_fn, &prm, 3, blob_ptr, blob_len, mh_proof_log_trace_heights(p), public_values, NUM_PUBLIC, state, pre,
                         MH_MIDEN_PRE_OBSERVE_FELTS, mh_proof_fields(p), mh_proof_num_fields(p), mh_proof_commitments(p),
                         mh_proof_num_commitments(p), nullptr, external_cb, &st, digest, err, err_cap);
+}
+
+// ExecutionTrace::check_constraints (processor/src/trace/mod.rs:261-278) of this statement: check.hip with the statement's challenger state,
+// pre-observe schedule and eval_external
+static int check_common(mh_ctx* ctx, const mh_miden* m, mh_trace* const* traces, const uint64_t* public_values, const uint64_t* aux_inputs,
+                        size_t n_aux_inputs, int flags, mh_check_entry* out, size_t cap, size_t* n_entries) {
+  if (!ctx || !m || m->ctx != ctx || !n_entries) return MH_ERR_INVALID;
+  mh_pcs_params prm;
+  mh_miden_pcs_params(&prm);
+  u64 pre[MH_MIDEN_PRE_OBSERVE_FELTS], state[12];
+  if (mh_miden_pre_observe(&prm, public_values, aux_inputs, n_aux_inputs, pre) != MH_OK) {
+    ctx->err = "mh_check_miden: 32 public values and aux inputs = program hash (4) | deferred root (4) | kernel digests (4 each, <= 255) expected";
+    return MH_ERR_INVALID;
+  }
+  mh_miden_challenger_state(state);
+  Statement st{aux_inputs, n_aux_inputs};
+  static const char* const names[3] = {"core", "chiplets", "poseidon2"};
+  return check_statement(ctx, 3, m->airs, traces, nullptr, public_values, NUM_PUBLIC, state, pre, MH_MIDEN_PRE_OBSERVE_FELTS, external_cb, &st,
+                         names, flags, out, cap, n_entries);
+}
+
+int mh_check_miden(mh_ctx* ctx, const mh_miden* m, const uint64_t* core_rowmajor, int log_core, const uint64_t* chiplets_rowmajor,
+                   int log_chiplets, const uint64_t* poseidon2_rowmajor, int log_poseidon2, const uint64_t* public_values,
+                   const uint64_t* aux_inputs, size_t n_aux_inputs, int flags, mh_check_entry* out, size_t cap, size_t* n_entries) {
+  if (!ctx || !m || m->ctx != ctx) return MH_ERR_INVALID;
+  const uint64_t* rm[3] = {core_rowmajor, chiplets_rowmajor, poseidon2_rowmajor};
+  const int lh[3] = {log_core, log_chiplets, log_poseidon2};
+  mh_trace* tr[3] = {nullptr, nullptr, nullptr};
+  int rc = MH_OK;
+  for (int i = 0; i < 3 && rc == MH_OK; i++) {
+    if (!rm[i] || lh[i] < 1 || lh[i] > 30) {
+      ctx->err = "mh_check_miden: null matrix or log height outside 1..30";
+      rc = MH_ERR_INVALID;
+    } else {
+      rc = mh_trace_upload(ctx, rm[i], lh[i], m->airs[i]->main_width, &tr[i]);
+    }
+  }
+  if (rc == MH_OK) rc = check_common(ctx, m, tr, public_values, aux_inputs, n_aux_inputs, flags, out, cap, n_entries);
+  for (mh_trace* t : tr) mh_trace_free(t);
+  return rc;
+}
+int mh_check_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* const traces[3], const uint64_t* public_values, const uint64_t* aux_inputs,
+                          size_t n_aux_inputs, int flags, mh_check_entry* out, size_t cap, size_t* n_entries) {
+  if (!traces) return MH_ERR_INVALID;
+  return check_common(ctx, m, traces, public_values, aux_inputs, n_aux_inputs, flags, out, cap, n_entries);
 }
 
 }  // extern "C"

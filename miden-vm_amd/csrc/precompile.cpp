@@ -19,6 +19,8 @@
 #include "../../include/midenhip.h"
 #include "ctx.hpp"
 #include "gl.cuh"
+#include "air.hpp"
+#include "kernels.hpp"
 #include <cstring>
 #include <memory>
 #include <string>
@@ -238,6 +240,51 @@ int mh_verify_precompile(int hash_fn, const uint64_t preprocessed_root[4], const
   return mh_verify_lmcs(hash_fn, &prm, N_AIRS, blob_ptr, blob_len, mh_proof_log_trace_heights(p), pub, N_PUBLIC, state, pre,
                         MH_PRECOMPILE_PRE_OBSERVE_FELTS, mh_proof_fields(p), mh_proof_num_fields(p), mh_proof_commitments(p),
                         mh_proof_num_commitments(p), preprocessed_root, mh_external_precompile_session, nullptr, digest, err, err_cap);
+}
+
+// SessionTraces::check (session/prove.rs:269-275): check.hip with the session's challenger state, the pre-observe schedule with 0^4 in
+// place of the preprocessed commitment (no commitment is made), and ChipletMultiAir::eval_external
+static int check_common(mh_ctx* ctx, mh_precompile* s, mh_trace* const* traces, const uint64_t* public_root, int flags, mh_check_entry* out,
+                        size_t cap, size_t* n_entries) {
+  if (!ctx || !s || s->ctx != ctx || !public_root || !n_entries) return MH_ERR_INVALID;
+  mh_pcs_params prm;
+  mh_precompile_pcs_params(&prm);
+  u64 pre[MH_PRECOMPILE_PRE_OBSERVE_FELTS], state[12] = {0};
+  const u64 no_root[4] = {0, 0, 0, 0};
+  int rc = mh_precompile_pre_observe(&prm, no_root, public_root, pre);
+  if (rc != MH_OK) return rc;
+  u64 pub[N_PUBLIC];
+  for (size_t i = 0; i < N_PUBLIC; i++) pub[i] = gl_canon(public_root[i]);
+  const mh_trace* preps[N_AIRS] = {};
+  preps[BYTE_PAIR_LUT] = s->table;  // the raw table: the AIR's attachment (made by the provers) is not touched
+  static const char* const names[N_AIRS] = {"chunk_node", "poseidon2", "keccak_round", "byte_pair_lut", "keccak_sponge", "transcript_eval",
+                                            "uint_store_mul", "uint_add", "ec_groups", "ec_point_store", "ec_group_add", "ec_msm"};
+  return check_statement(ctx, N_AIRS, s->airs, traces, preps, pub, N_PUBLIC, state, pre, MH_PRECOMPILE_PRE_OBSERVE_FELTS,
+                         mh_external_precompile_session, nullptr, names, flags, out, cap, n_entries);
+}
+
+int mh_check_precompile(mh_ctx* ctx, mh_precompile* s, const uint64_t* const mains_rowmajor[MH_PRECOMPILE_NUM_AIRS],
+                        const int log_heights[MH_PRECOMPILE_NUM_AIRS], const uint64_t public_root[4], int flags, mh_check_entry* out, size_t cap,
+                        size_t* n_entries) {
+  if (!ctx || !s || s->ctx != ctx || !mains_rowmajor || !log_heights) return MH_ERR_INVALID;
+  mh_trace* tr[N_AIRS] = {};
+  int rc = MH_OK;
+  for (int i = 0; i < N_AIRS && rc == MH_OK; i++) {
+    if (!mains_rowmajor[i] || log_heights[i] < 1 || log_heights[i] > 30) {
+      ctx->err = "mh_check_precompile: null matrix or log height outside 1..30";
+      rc = MH_ERR_INVALID;
+    } else {
+      rc = mh_trace_upload(ctx, mains_rowmajor[i], log_heights[i], s->airs[i]->main_width, &tr[i]);
+    }
+  }
+  if (rc == MH_OK) rc = check_common(ctx, s, tr, public_root, flags, out, cap, n_entries);
+  for (mh_trace* t : tr) mh_trace_free(t);
+  return rc;
+}
+int mh_check_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_trace* const traces[MH_PRECOMPILE_NUM_AIRS], const uint64_t public_root[4],
+                               int flags, mh_check_entry* out, size_t cap, size_t* n_entries) {
+  if (!traces) return MH_ERR_INVALID;
+  return check_common(ctx, s, traces, public_root, flags, out, cap, n_entries);
 }
 
 }  // extern "C"

@@ -432,3 +432,87 @@ void quotient_upsample_accumulate(mh_ctx* c, const u64* q_small, int log_n, int 
     MH_LAUNCH(k_quot_regroup_accumulate, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, lde.u(), log_n, log_dj,
                        log_d, acc_in, log_n_prev, beta, acc_out, t_first, n_local);
 }
+
+// The constraint checker's screen (check.hip): the same constraint program, on the trace domain itself -- one "coset" (B = D = 1, point q
+// IS row r, as logup.hip runs lookup programs), coset_tab = {1, 1, 1} (x = w_n^r, Z_H = 1/Z_H = 1), the caller's inv_first / inv_last =
+// [r == 0] / [r == n-1] and wh_inv = w_n^-1 (sel_trans = w^r - w^-1 vanishes on the last row only).  `acc` ([2][n]) receives
+// F(r) = sum_k alpha^(K-1-k) s_k(r) C_k(r), any representative.  Host code only: the kernels and the programs above are the proving path's.
+void constraint_fold_trace_domain(mh_ctx* c, const mh_air* air, const mh_trace* main, const mh_trace* aux, const mh_trace* prep,
+                                  const u64* inv_first, const u64* inv_last, const std::vector<u64>& publics, const std::vector<e2>& randomness,
+                                  const std::vector<e2>& aux_values, e2 alpha, u64* acc) {
+  const int log_n = main->log_n;
+  const size_t n = (size_t)1 << log_n;
+  const size_t K = air->n_constraints;
+  std::vector<u64> tab = {1, 1, 1}, apow(2 * std::max<size_t>(K, 1));
+  {
+    e2 p = e2_make(1);
+    for (size_t k = K; k-- > 0;) {
+      apow[2 * k] = p.c0;
+      apow[2 * k + 1] = p.c1;
+      p = e2_mul(p, alpha);
+    }
+  }
+  const size_t Pm = air->max_period(), prow = Pm ? Pm : 1;  // the raw periodic columns, tiled to the longest period: row r reads r mod prow
+  std::vector<u64> ptab(std::max<size_t>(1, air->periodic.size() * prow), 0);
+  for (size_t col = 0; col < air->periodic.size(); col++)
+    for (size_t i = 0; i < prow; i++) ptab[col * prow + i] = air->periodic[col][i % air->periodic[col].size()] % GL_P;
+  std::vector<u64> pub(std::max<size_t>(1, publics.size())), rnd(2 * std::max<size_t>(1, randomness.size())),
+      av(2 * std::max<size_t>(1, aux_values.size()));
+  for (size_t i = 0; i < publics.size(); i++) pub[i] = gl_canon(publics[i]);
+  for (size_t i = 0; i < randomness.size(); i++) { rnd[2 * i] = randomness[i].c0; rnd[2 * i + 1] = randomness[i].c1; }
+  for (size_t i = 0; i < aux_values.size(); i++) { av[2 * i] = aux_values[i].c0; av[2 * i + 1] = aux_values[i].c1; }
+  std::vector<u64> blob;
+  auto put = [&](const std::vector<u64>& v) {
+    size_t off = blob.size();
+    blob.insert(blob.end(), v.begin(), v.end());
+    return off;
+  };
+  const size_t o_tab = put(tab), o_ap = put(apow), o_pt = put(ptab), o_pub = put(pub), o_rnd = put(rnd), o_av = put(av);
+  DevBuf dblob(blob.size() * 8);
+  c->h2d(dblob.p, blob.data(), blob.size() * 8);
+  const u64* tw = c->twiddles(log_n, false);
+  const u64 wh_inv = gl_inv(gl_two_adic_generator(log_n));
+  const u64* aux_cols = aux ? aux->cols.u() : main->cols.u();  // an AIR without aux columns never reads them
+  HIP_CHECK(hipMemsetAsync(acc, 0, 2 * n * 8, c->stream));
+  if (air->jit && !(jit_program_fused(air->jit) && log_n < 8)) {
+    JitArgs j{};
+    j.main_lde = main->cols.u(); j.aux_lde = aux_cols;
+    j.prep_lde = prep ? prep->cols.u() : nullptr;
+    j.acc = acc;
+    j.tw = tw; j.coset_tab = dblob.u() + o_tab;
+    j.inv_first = inv_first; j.inv_last = inv_last;
+    j.periodic = dblob.u() + o_pt; j.periodic_rows = (u32)prow;
+    j.publics = dblob.u() + o_pub; j.randomness = dblob.u() + o_rnd; j.aux_values = dblob.u() + o_av;
+    j.alpha_pows = dblob.u() + o_ap;
+    j.wh_inv = wh_inv;
+    j.log_n = log_n;  // log_cosets = log_d = log_dl = jc_shift = t0 = 0; acc_in = null: 1/Z_H = 1 leaves the fold as it is
+    ProfScope ps(c, "check_screen", (double)n * (8.0 * air->touched_base_columns + 16.0));
+    jit_quotient_run(c, air->jit, j, n);
+    return;
+  }
+  QuotArgs a{};
+  a.code = (const AirIns*)air->d_code.p;
+  a.n_ins = (u32)air->code.size();
+  a.n_slots = air->n_slots;
+  a.main_lde = main->cols.u();
+  a.aux_lde = aux_cols;
+  a.prep_lde = prep ? prep->cols.u() : nullptr;
+  a.log_n = log_n;
+  a.tw = tw;
+  a.coset_tab = dblob.u() + o_tab;
+  a.wh_inv = wh_inv;
+  a.inv_first = inv_first; a.inv_last = inv_last;
+  a.periodic = dblob.u() + o_pt;
+  a.periodic_rows = (u32)prow;
+  a.publics = dblob.u() + o_pub; a.randomness = dblob.u() + o_rnd; a.aux_values = dblob.u() + o_av;
+  a.alpha_pows = dblob.u() + o_ap;
+  a.acc_out = acc;
+  unsigned T = 256;
+  while (T > 64 && (size_t)air->n_slots * 16 * T > 48 * 1024) T >>= 1;
+  const size_t lds = (size_t)air->n_slots * 16 * T;
+  MH_REQUIRE(lds <= 160 * 1024, "constraint DAG needs more live values than fit in LDS (160 KiB per workgroup)");
+  if (lds > 64 * 1024)
+    HIP_CHECK(hipFuncSetAttribute((const void*)k_eval_quotient, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  ProfScope ps(c, "check_screen", (double)n * (8.0 * air->touched_base_columns + 16.0));
+  MH_LAUNCH(k_eval_quotient, dim3((unsigned)((n + T - 1) / T)), dim3(T), lds, c->stream, a);
+}
