@@ -13,8 +13,9 @@
 //   * one fold back to 64 bits per element per S-box (2^64 = 2^32 - 1 mod p);
 //   * the 22 internal rounds keep elements 1..11 wide across rounds; the fractional diagonal
 //     [-2,1,2,1/2,3,4,-1/2,-3,-4,1/4,-1/4,1/8] is cleared by carrying the whole state scaled by c_r = 2 * 8^r
-//     (integer diagonal [-16,8,16,4,24,32,-4,-24,-32,2,-2,1]); the S-box of round r then costs one
-//     extra multiplication by the constant c_r^(-6), and wide values are refolded every 4 rounds;
+//     (integer diagonal [-16,8,16,4,24,32,-4,-24,-32,2,-2,1]); the S-box output of round r is then scaled by
+//     c_r^(-6), a power of two: a shift into signed wide words (p2f_shl_words), not a product; wide values are refolded
+//     every 4 rounds, and the internal rounds are unrolled so that each exponent is a compile-time constant;
 //   * the diagonal pairs (+k, -k) -- elements (3,6), (4,7), (5,8), (9,10) -- are carried as h = (x_i + x_j)/2, whose
 //     two-step recurrence h(r+1) = k^2 h(r-1) + 8*sum is ONE shift-add per part and round (no 64-bit subtraction, which is
 //     two instructions plus the shift), and the sum reads one value per pair; tests/test_p2_fast_schedule.py checks the algebra
@@ -292,6 +293,64 @@ __device__ __forceinline__ u64 p2f_fold_signed(u64 L, u64 H) {
   return p2f_fold(L + BL, H + BH);
 }
 
+// Multiplication by a power of two, y * 2^E (mod p) for any y < 2^64 and a compile-time E in [0, 192): the round-scale and
+// de-scale constants of the scaled internal rounds are all powers of two (p2_fast_constants.inc: *_LOG2), so they cost a shift
+// and sign changes instead of a 13-instruction product.  E = 96 s + 32 q + b (b < 32): y * 2^b = u0 + u1 2^32 + u2 2^64 with
+// u2 = y >> (64 - b) < 2^b, and 2^64 = 2^32 - 1, 2^96 = -1 (mod p) give the signed wide pair (L, H), each part +-word +-word:
+//     q = 0: L = u0 - u2, H = u1 + u2;   q = 1: L = -u1 - u2, H = u0 + u1;   q = 2: L = -u0 - u1, H = u0 - u2;   s = 1 negates.
+// |L|, |H| < 2^33.  The words are never summed on their own: each goes straight into the accumulator that consumes the part.
+__host__ __device__ constexpr int p2f_shl_sign(int E, int part, int w) {
+  constexpr int tab[3][2][3] = {{{1, 0, -1}, {0, 1, 1}}, {{0, -1, -1}, {1, 1, 0}}, {{-1, -1, 0}, {1, 0, -1}}};
+  const int e = E % 96, sg = tab[e / 32][part][w] * (E >= 96 ? -1 : 1);
+  return (w == 2 && e % 32 == 0) ? 0 : sg;  // b = 0: no spilled word
+}
+template <int E>
+__device__ __forceinline__ void p2f_shl_words(u64 y, u32 (&u)[3]) {
+  static_assert(E >= 0 && E < 192, "exponent out of range");
+  constexpr int b = E % 96 % 32;
+  const u64 z = y << b;
+  u[0] = lo32(z);
+  u[1] = hi32(z);
+  if constexpr (b > 0) u[2] = hi32(y) >> (32 - b);
+  else u[2] = 0;
+}
+// acc + SG * u for a 32-bit word: one v_mad_u64_u32 for +1, a 64-bit subtraction (v_sub_co + v_subb_co) for -1
+template <int SG>
+__device__ __forceinline__ u64 p2f_acc_word(u64 acc, u32 u) {
+  if constexpr (SG > 0) return p2f_mad<1>(acc, u);
+  else if constexpr (SG < 0) return acc - (u64)u;
+  else return acc;
+}
+// acc + SG * (part PART of y 2^E), the words of y 2^E from p2f_shl_words<E>
+template <int E, int PART, int SG>
+__device__ __forceinline__ u64 p2f_acc_shl(u64 acc, const u32 (&u)[3]) {
+  acc = p2f_acc_word<SG * p2f_shl_sign(E, PART, 0)>(acc, u[0]);
+  acc = p2f_acc_word<SG * p2f_shl_sign(E, PART, 1)>(acc, u[1]);
+  return p2f_acc_word<SG * p2f_shl_sign(E, PART, 2)>(acc, u[2]);
+}
+// F(std::integral_constant<int, r>{}) for r = 0 .. 21: the internal rounds unrolled with r a compile-time constant
+#define P2F_IC(F, r) F(std::integral_constant<int, r>{})
+#define P2F_ROUNDS22(F)                                                                                               \
+  do {                                                                                                                \
+    P2F_IC(F, 0); P2F_IC(F, 1); P2F_IC(F, 2); P2F_IC(F, 3); P2F_IC(F, 4); P2F_IC(F, 5); P2F_IC(F, 6); P2F_IC(F, 7);          \
+    P2F_IC(F, 8); P2F_IC(F, 9); P2F_IC(F, 10); P2F_IC(F, 11); P2F_IC(F, 12); P2F_IC(F, 13); P2F_IC(F, 14); P2F_IC(F, 15);    \
+    P2F_IC(F, 16); P2F_IC(F, 17); P2F_IC(F, 18); P2F_IC(F, 19); P2F_IC(F, 20); P2F_IC(F, 21);                             \
+  } while (0)
+// One part of an internal round's two sums: s8 = 8 (R + y 2^E) and n = 8 (R - y 2^E).  The side with more added words is built
+// word by word (a mad each), the other one as 16 R - that side.
+template <int E, int PART>
+__device__ __forceinline__ void p2f_pm_shl(u64 R, const u32 (&u)[3], u64& s8, u64& n) {
+  constexpr int plus = (p2f_shl_sign(E, PART, 0) > 0) + (p2f_shl_sign(E, PART, 1) > 0) + (p2f_shl_sign(E, PART, 2) > 0);
+  constexpr int minus = (p2f_shl_sign(E, PART, 0) < 0) + (p2f_shl_sign(E, PART, 1) < 0) + (p2f_shl_sign(E, PART, 2) < 0);
+  if constexpr (plus >= minus) {
+    s8 = p2f_acc_shl<E, PART, 1>(R, u) << 3;
+    n = (R << 4) - s8;
+  } else {
+    n = p2f_acc_shl<E, PART, -1>(R, u) << 3;
+    s8 = (R << 4) - n;
+  }
+}
+
 // out = circ(2*M4, M4, M4) * s (+ rc), s given as 64-bit values; result folded back to 64 bits.
 // M4 = [[2,3,1,1],[1,2,3,1],[1,1,2,3],[3,1,1,2]]  (poseidon2/mod.rs:233-281)
 template <bool RC>
@@ -354,7 +413,8 @@ __device__ __forceinline__ void p2f_permute(u64 s[12]) {
   u64 X1L, X1H, X2L, X2H, X11L, X11H;
   u64 AL[4], AH[4], BL[4], BH[4];  // pair q: A = h(even round), B = h(odd round)
   {
-    const u64 y = p2f_mul_k(p2f_sbox(t0), p2c::P2G_K[0]);
+    u32 y[3];  // the words of y = K_0 x^7 (p2f_shl_words)
+    p2f_shl_words<p2c::P2G_K_LOG2[0]>(p2f_sbox(t0), y);
     u64 RL = p2f_zmul<1>(lo32(s[1])), RH = p2f_zmul<1>(hi32(s[1]));
 #pragma unroll
     for (int i = 2; i < 12; i++) {
@@ -362,10 +422,12 @@ __device__ __forceinline__ void p2f_permute(u64 s[12]) {
       RH = p2f_mad<1>(RH, hi32(s[i]));
     }
     // sum = y + 2 * (x_1 + ... + x_11);  element 0: -16 y + 8 sum = 8 * (2 R - y)
-    const u64 s8L = p2f_mad<1>(RL << 1, lo32(y)) << 3, s8H = p2f_mad<1>(RH << 1, hi32(y)) << 3;
+    u64 s8L, s8H, nL, nH;
+    p2f_pm_shl<p2c::P2G_K_LOG2[0], 0>(RL << 1, y, s8L, nL);
+    p2f_pm_shl<p2c::P2G_K_LOG2[0], 1>(RH << 1, y, s8H, nH);
     {
       const u64 rc = p2c::P2G_ARK[1];
-      t0 = p2f_fold_signed((((RL << 1) - (u64)lo32(y)) << 3) + (rc & 0xFFFFFFFFULL), (((RH << 1) - (u64)hi32(y)) << 3) + (rc >> 32));
+      t0 = p2f_fold_signed(nL + (rc & 0xFFFFFFFFULL), nH + (rc >> 32));
     }
     X1L = p2f_mad<16>(s8L, lo32(s[1])), X1H = p2f_mad<16>(s8H, hi32(s[1]));     // 8 * (2 x)
     X2L = p2f_mad<32>(s8L, lo32(s[2])), X2H = p2f_mad<32>(s8H, hi32(s[2]));     // 16 * (2 x)
@@ -384,12 +446,14 @@ __device__ __forceinline__ void p2f_permute(u64 s[12]) {
   // round r: C = h(r), P = h(r - 1) -> P = h(r + 1)
 #define P2G_ROUND(r, CL, CH, PL, PH, HAS_RC)                                                             \
   {                                                                                                       \
-    const u64 y = p2f_mul_k(p2f_sbox(t0), p2c::P2G_K[r]);                                                   \
+    u32 y[3]; /* the words of y = K_r x^7: K_r = 2^e, a shift (p2f_shl_words) */                           \
+    p2f_shl_words<p2c::P2G_K_LOG2[r]>(p2f_sbox(t0), y);                                                   \
     const u64 RL = ((CL[0] + CL[1] + CL[2] + CL[3]) << 1) + X1L + X2L + X11L;                             \
     const u64 RH = ((CH[0] + CH[1] + CH[2] + CH[3]) << 1) + X1H + X2H + X11H;                             \
-    const u64 s8L = p2f_mad<1>(RL, lo32(y)) << 3, s8H = p2f_mad<1>(RH, hi32(y)) << 3;                     \
+    u64 s8L, s8H, nL, nH; /* 8 (R + y) and -16 y + 8 (R + y) = 8 (R - y) */                                \
+    p2f_pm_shl<p2c::P2G_K_LOG2[r], 0>(RL, y, s8L, nL);                                                    \
+    p2f_pm_shl<p2c::P2G_K_LOG2[r], 1>(RH, y, s8H, nH);                                                    \
     {                                                                                                     \
-      u64 nL = (RL - (u64)lo32(y)) << 3, nH = (RH - (u64)hi32(y)) << 3; /* -16 y + 8 (R + y) */           \
       if (HAS_RC) {                                                                                       \
         const u64 rc = p2c::P2G_ARK[(r) + 1];                                                             \
         nL += rc & 0xFFFFFFFFULL;                                                                         \
@@ -416,10 +480,11 @@ __device__ __forceinline__ void p2f_permute(u64 s[12]) {
     L_ = p2f_zmul<1>(lo32(v));                    \
     H_ = p2f_zmul<1>(hi32(v));                    \
   }
-#pragma unroll 1
-  for (int r = 1; r < 22; r += 2) {
+  // rounds r and r + 1; unrolled (the exponent of the round scale is a template argument): r is a compile-time constant
+  const auto round_pair = [&](auto rr) {
+    constexpr int r = decltype(rr)::value;
     P2G_ROUND(r, BL, BH, AL, AH, r < 21)
-    if ((r & 3) == 3) {  // parts < 2^32 grow to < 2^60.5 in four rounds (tools/p2_pair_bounds.py): refold before 2^61
+    if constexpr ((r & 3) == 3) {  // parts < 2^32 grow to < 2^60.6 in four rounds (tools/p2_pair_bounds.py): refold before 2^61
       P2G_REFOLD(X1L, X1H)
       P2G_REFOLD(X2L, X2H)
       P2G_REFOLD(X11L, X11H)
@@ -429,8 +494,19 @@ __device__ __forceinline__ void p2f_permute(u64 s[12]) {
         P2G_REFOLD(BL[q], BH[q])
       }
     }
-    if (r + 1 < 22) P2G_ROUND(r + 1, AL, AH, BL, BH, true)
-  }
+    if constexpr (r + 1 < 22) P2G_ROUND(r + 1, AL, AH, BL, BH, true)
+  };
+  round_pair(std::integral_constant<int, 1>{});
+  round_pair(std::integral_constant<int, 3>{});
+  round_pair(std::integral_constant<int, 5>{});
+  round_pair(std::integral_constant<int, 7>{});
+  round_pair(std::integral_constant<int, 9>{});
+  round_pair(std::integral_constant<int, 11>{});
+  round_pair(std::integral_constant<int, 13>{});
+  round_pair(std::integral_constant<int, 15>{});
+  round_pair(std::integral_constant<int, 17>{});
+  round_pair(std::integral_constant<int, 19>{});
+  round_pair(std::integral_constant<int, 21>{});
 #undef P2G_ROUND
 #undef P2G_REFOLD
   // A = h(22), B = h(21): back to the elements, out of the scaled domain (factor c_22), then the first terminal round constants

@@ -53,7 +53,7 @@ __device__ __forceinline__ u64 p2l_external(u64 s, int g, u64 c) {
 __device__ __forceinline__ u64 p2l_permute(u64 s) {
   const int lane = threadIdx.x & 63, g = lane & 15;
   // A lone wave pays every memory latency in its dependency chain: the round constants are fetched up front (the eight external
-  // ones of this lane here, in one latency; the internal ones one round ahead, below), not where the rounds use them.
+  // ones of this lane here, in one latency; the internal ones at fixed offsets the scheduler can hoist), not where the rounds use them.
   const int gi = g < 12 ? g : 0;
   u64 rci[4], rct[4];
 #pragma unroll
@@ -82,10 +82,10 @@ __device__ __forceinline__ u64 p2l_permute(u64 s) {
   // T_0' = 8 S - 16 y (+ round constant) comes out the same in every lane (S and y are row-uniform).
   u64 L = (g >= 1 && g < 12) ? (u64)lo32(s) : 0, H = (g >= 1 && g < 12) ? (u64)hi32(s) : 0;
   u64 nL = 0, nH = 0;
-  u64 k_cur = p2c::P2F_INT_K[0], a_cur = p2c::P2F_ARK_INT_SCALED[1];
-#pragma unroll 1
-  for (int r = 0; r < 22; r++) {
-    const u64 k_nxt = p2c::P2F_INT_K[r < 21 ? r + 1 : 21], a_nxt = p2c::P2F_ARK_INT_SCALED[r < 20 ? r + 2 : 21];  // for the next round
+  // unrolled: the round scale K_r = 2^e is a shift whose exponent is a template argument (p2f_shl_words); the scaled round
+  // constants are read at fixed offsets, which the scheduler may hoist ahead of the chain
+  const auto round = [&](auto rr) {
+    constexpr int r = decltype(rr)::value, E = p2c::P2F_INT_K_LOG2[r];
     u64 sL = L, sH = H;  // R: sum over the 16 lanes of the row (lane 0 and the idle lanes hold zeros), left in every lane
     sL += p2l_dpp<P2L_ROW_ROR(8)>(sL); sH += p2l_dpp<P2L_ROW_ROR(8)>(sH);
     sL += p2l_dpp<P2L_ROW_ROR(4)>(sL); sH += p2l_dpp<P2L_ROW_ROR(4)>(sH);
@@ -93,25 +93,26 @@ __device__ __forceinline__ u64 p2l_permute(u64 s) {
     sL += p2l_dpp<P2L_QUAD(1, 0, 3, 2)>(sL); sH += p2l_dpp<P2L_QUAD(1, 0, 3, 2)>(sH);
     const u64 mL = L * mag, mH = H * mag;
     const u64 cL = (mL ^ sgn) - sgn, cH = (mH ^ sgn) - sgn;  // c_i T_i (two's complement arithmetic on the signed wide parts)
-    const u64 y = p2l_dpp<P2L_ROW_BCAST0>(p2f_mul(p2f_sbox(t0), k_cur));  // the S-box output (lane 0's; t0 is row-uniform from round 1 on)
-    const u64 yl = lo32(y), yh = hi32(y);
-    sL += yl;
-    sH += yh;
-    L = (sL << 3) + cL;  // T_i' = 8 S + c_i T_i
-    H = (sH << 3) + cH;
-    nL = (sL << 3) - (yl << 4);  // T_0' = 8 S - 16 y
-    nH = (sH << 3) - (yh << 4);
+    u32 y[3];  // the words of the S-box output y = K_r x^7 (lane 0's x^7; t0 is row-uniform from round 1 on)
+    p2f_shl_words<E>(p2l_dpp<P2L_ROW_BCAST0>(p2f_sbox(t0)), y);
+    u64 s8L, s8H;
+    p2f_pm_shl<E, 0>(sL, y, s8L, nL);  // 8 S = 8 (R + y) and T_0' = 8 S - 16 y = 8 (R - y)
+    p2f_pm_shl<E, 1>(sH, y, s8H, nH);
+    L = s8L + cL;  // T_i' = 8 S + c_i T_i
+    H = s8H + cH;
     if (g == 0 || g >= 12) { L = 0; H = 0; }
-    if (r < 21) t0 = p2f_fold_signed(nL + (a_cur & 0xFFFFFFFFULL), nH + (a_cur >> 32));
-    k_cur = k_nxt;
-    a_cur = a_nxt;
-    if ((r & 3) == 3) {  // refold the wide parts before they outgrow 2^61 (<= 7 bits per round)
+    if constexpr (r < 21) {
+      const u64 a = p2c::P2F_ARK_INT_SCALED[r + 1];
+      t0 = p2f_fold_signed(nL + (a & 0xFFFFFFFFULL), nH + (a >> 32));
+    }
+    if constexpr ((r & 3) == 3) {  // refold the wide parts before they outgrow 2^61 (<= 7 bits per round)
       const u64 v = p2f_fold_signed(L, H);
       L = lo32(v);
       H = hi32(v);
       if (g == 0 || g >= 12) { L = 0; H = 0; }
     }
-  }
+  };
+  P2F_ROUNDS22(round);
   if (g == 0) {  // element 0 after the last round
     L = nL;
     H = nH;

@@ -50,7 +50,7 @@ __device__ __forceinline__ void p2q_sbox3(u64 (&s)[3]) {
 // One permutation per quad; lane j holds elements j, 4 + j, 8 + j on entry and exit (canonical on exit).
 __device__ __forceinline__ void p2q_permute(u64 (&s)[3]) {
   const int j = threadIdx.x & 3;
-  // the 24 external round constants of this lane up front, the internal ones one round ahead: a lone wave pays every memory latency
+  // the 24 external round constants of this lane up front, the internal ones at fixed offsets the scheduler can hoist: a lone wave pays every memory latency
   // that sits in its dependency chain (poseidon2_lanes.cuh)
   u64 rci[4][3], rct[4][3];
 #pragma unroll
@@ -81,14 +81,15 @@ __device__ __forceinline__ void p2q_permute(u64 (&s)[3]) {
   }
   u64 t0 = p2f_add_canon(s[0], p2c::P2F_ARK_INT_SCALED[0]);  // used from lane 0 only
   if (j == 0) { L[0] = 0; H[0] = 0; }
-  u64 k_cur = p2c::P2F_INT_K[0], a_cur = p2c::P2F_ARK_INT_SCALED[1];
-#pragma unroll 1
-  for (int r = 0; r < 22; r++) {
-    const u64 k_nxt = p2c::P2F_INT_K[r < 21 ? r + 1 : 21], a_nxt = p2c::P2F_ARK_INT_SCALED[r < 20 ? r + 2 : 21];  // for the next round
-    const u64 y = p2l_dpp<P2L_QUAD(0, 0, 0, 0)>(p2f_mul(p2f_sbox(t0), k_cur));  // lane 0's S-box output
-    if (j == 0) {
-      L[0] = lo32(y);
-      H[0] = hi32(y);
+  // unrolled: the round scale K_r = 2^e is a shift whose exponent is a template argument (p2f_shl_words); the scaled round
+  // constants are read at fixed offsets, which the scheduler may hoist ahead of the chain
+  const auto round = [&](auto rr) {
+    constexpr int r = decltype(rr)::value, E = p2c::P2F_INT_K_LOG2[r];
+    u32 y[3];  // the words of lane 0's S-box output y = K_r x^7
+    p2f_shl_words<E>(p2l_dpp<P2L_QUAD(0, 0, 0, 0)>(p2f_sbox(t0)), y);
+    if (j == 0) {  // the signed wide pair of y (|part| < 2^33)
+      L[0] = p2f_acc_shl<E, 0, 1>(0, y);
+      H[0] = p2f_acc_shl<E, 1, 1>(0, y);
     }
     u64 sL = L[0] + L[1] + L[2], sH = H[0] + H[1] + H[2];  // the sum over the 12 elements, left in every lane of the quad
     sL += p2l_dpp<P2L_QUAD(1, 0, 3, 2)>(sL); sH += p2l_dpp<P2L_QUAD(1, 0, 3, 2)>(sH);
@@ -100,14 +101,13 @@ __device__ __forceinline__ void p2q_permute(u64 (&s)[3]) {
       H[k] = (sH << 3) + ((mH ^ sgn[k]) - sgn[k]);
     }
     u64 nL = L[0], nH = H[0];  // lane 0: next S-box input = T_0' + scaled round constant, folded
-    if (r < 21) {
-      nL += a_cur & 0xFFFFFFFFULL;
-      nH += a_cur >> 32;
+    if constexpr (r < 21) {
+      const u64 a = p2c::P2F_ARK_INT_SCALED[r + 1];
+      nL += a & 0xFFFFFFFFULL;
+      nH += a >> 32;
     }
     t0 = p2f_fold_signed(nL, nH);
-    k_cur = k_nxt;
-    a_cur = a_nxt;
-    if ((r & 3) == 3) {  // refold the wide parts before they outgrow 2^61 (<= 7 bits per round)
+    if constexpr ((r & 3) == 3) {  // refold the wide parts before they outgrow 2^61 (<= 7 bits per round)
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         const u64 v = p2f_fold_signed(L[k], H[k]);
@@ -115,7 +115,8 @@ __device__ __forceinline__ void p2q_permute(u64 (&s)[3]) {
         H[k] = hi32(v);
       }
     }
-  }
+  };
+  P2F_ROUNDS22(round);
   // leave the scaled domain, first terminal round constants
 #pragma unroll
   for (int k = 0; k < 3; k++) s[k] = p2f_add_canon(p2f_mul(p2f_fold_signed(L[k], H[k]), p2c::P2F_DESCALE), rct[0][k]);

@@ -1,5 +1,5 @@
-"""Worst-case magnitude of the wide parts (L, H) in the paired internal rounds of poseidon2_fast.cuh (p2f_permute): inputs and
-S-box outputs have parts < 2^32; p2f_fold_signed needs |part| < 2^61.  Prints log2 of the largest part after every round for three
+"""Worst-case magnitude of the wide parts (L, H) in the paired internal rounds of poseidon2_fast.cuh (p2f_permute): inputs have
+parts < 2^32, the scaled S-box outputs y * 2^e (p2f_shl_words: a signed sum of two 32-bit words per part) |parts| < 2^33; p2f_fold_signed needs |part| < 2^61.  Prints log2 of the largest part after every round for three
 refold schedules; the kernel refolds after rounds 3, 7, 11, 15, 19 (first line).
 Usage: python tools/p2_pair_bounds.py"""
 import math
@@ -7,7 +7,7 @@ B32 = 2**32
 def run(refold_after):
     # round 0
     x = B32  # parts of inputs
-    y = B32
+    y = 2 * B32  # y * 2^e as shifted words
     R = 11 * x
     S = 2 * R + y
     s8 = 8 * S
