@@ -30,6 +30,30 @@ pub struct mh_check_entry {
     pub value: [u64; 2],
 }
 
+/// mh_balance_entry.first_push: the push list was not collected (more than 2^22 pushes).
+pub const MH_BALANCE_NO_PUSHES: u64 = u64::MAX;
+
+/// An encoded denominator whose net multiplicity is not zero (mh_check_balance*; the reference's `Unmatched`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_balance_entry {
+    pub denom: [u64; 2],
+    pub net: [u64; 2],
+    pub pushes: u64,
+    pub first_push: u64,
+}
+
+/// A live push that landed on a reported denominator (the reference's `PushRecord` without msg_repr); instance -1: a boundary push.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_balance_push {
+    pub instance: i32,
+    pub column: u32,
+    pub fraction: u32,
+    pub row: u64,
+    pub multiplicity: [u64; 2],
+}
+
 /// PcsParams (crates/lifted-stark/src/pcs/params.rs:52-96).
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -223,4 +247,9 @@ unsafe extern "C" {
     pub fn mh_check_miden_traces(ctx: *mut mh_ctx, m: *const mh_miden, traces: *const *mut mh_trace, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize) -> c_int;
     pub fn mh_check_precompile(ctx: *mut mh_ctx, s: *mut mh_precompile, mains_rowmajor: *const *const u64, log_heights: *const c_int, public_root: *const u64, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize) -> c_int;
     pub fn mh_check_precompile_traces(ctx: *mut mh_ctx, s: *mut mh_precompile, traces: *const *mut mh_trace, public_root: *const u64, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize) -> c_int;
+    pub fn mh_check_balance(ctx: *mut mh_ctx, n: c_int, lookups: *const *const mh_lookup, traces: *const *const mh_trace, preprocessed: *const *const mh_trace, randomness: *const u64, n_randomness: usize, boundary_denoms: *const u64, boundary_signs: *const i32, n_boundary: usize, flags: c_int, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
+    pub fn mh_check_balance_miden(ctx: *mut mh_ctx, m: *const mh_miden, core_rowmajor: *const u64, log_core: c_int, chiplets_rowmajor: *const u64, log_chiplets: c_int, poseidon2_rowmajor: *const u64, log_poseidon2: c_int, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, flags: c_int, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
+    pub fn mh_check_balance_miden_traces(ctx: *mut mh_ctx, m: *const mh_miden, traces: *const *mut mh_trace, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, flags: c_int, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
+    pub fn mh_check_balance_precompile(ctx: *mut mh_ctx, s: *mut mh_precompile, mains_rowmajor: *const *const u64, log_heights: *const c_int, public_root: *const u64, flags: c_int, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
+    pub fn mh_check_balance_precompile_traces(ctx: *mut mh_ctx, s: *mut mh_precompile, traces: *const *mut mh_trace, public_root: *const u64, flags: c_int, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
 }

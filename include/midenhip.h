@@ -567,6 +567,64 @@ int mh_check_precompile(mh_ctx* ctx, mh_precompile* s, const uint64_t* const mai
 int mh_check_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_trace* const traces[MH_PRECOMPILE_NUM_AIRS], const uint64_t public_root[4],
                                int flags, mh_check_entry* out, size_t cap, size_t* n_entries);
 
+/* ---- bus balance: unmatched LogUp messages (air/src/lookup/debug/trace/mod.rs:44-95,161-189 check_trace_balance / BalanceReport /
+ * Unmatched / PushRecord; folded over a whole statement as precompiles-prover/src/tests/bus_balance.rs:25-108 does) -----------------
+ * Every constraint of every AIR holds on a trace whose buses do not balance; mh_check_* then reports one external entry and nothing
+ * else.  mh_check_balance* says WHICH messages are unmatched: it nets the multiplicities of all live pushes (canonical multiplicity
+ * != 0) of all instances plus the statement's boundary pushes per encoded denominator, and reports every denominator whose net
+ * multiplicity is not zero, with the pushes (instance, row, column, fraction, multiplicity) that landed on it.  Device stage:
+ * csrc/balance.hip, over the planes the lookup programs write (the aux traces are not built).
+ * Two stages: the screen sums m / d over all pushes and returns MH_OK when the sum is zero (unbalanced buses escape with probability
+ * about #pushes / p^2 over the challenges); otherwise, or under MH_CHECK_EXACT, the exact stage nets the pushes in an open-addressing
+ * table in device memory (load factor <= 1/2, 64-bit atomics only) and assembles the report.
+ * MH_OK: balanced.  MH_ERR_UNSATISFIED: not; mh_last_error names the first entry.  A live push whose denominator is zero is
+ * MH_ERR_INVALID.  *n_entries / *n_pushes = the exact totals, even when they exceed the caps; the first entry_cap / push_cap are written.
+ * Entries ascend by (denom[0], denom[1]); the push list holds the pushes of entry 0, then of entry 1, ..., each entry's pushes by
+ * (instance, row, column, fraction) with the boundary pushes (instance -1) last.  Two calls on the same input return the same bytes.
+ * At most 2^22 pushes are collected: when the entries' pushes are more, the entries come back complete (`pushes` exact) but with
+ * first_push = MH_BALANCE_NO_PUSHES and nothing is written to the push list; *n_pushes is still the exact total.
+ * Not in scope: PushRecord::msg_repr (the lookup blob does not carry payloads), MutualExclusionViolation (it does not carry groups),
+ * collect_column_oracle_folds. */
+#define MH_BALANCE_NO_PUSHES UINT64_MAX /* mh_balance_entry.first_push: the push list was not collected (internal bound) */
+typedef struct mh_balance_entry {   /* reference: Unmatched */
+  uint64_t denom[2];       /* canonical encoded denominator */
+  uint64_t net[2];         /* net signed multiplicity mod p (c1 = 0 for base-field multiplicities) */
+  uint64_t pushes;         /* live pushes that landed on it, exact */
+  uint64_t first_push;     /* index of its first push in the push list (entry order, then push order) */
+} mh_balance_entry;
+typedef struct mh_balance_push {    /* reference: PushRecord without msg_repr */
+  int32_t instance;        /* -1: a boundary push of the statement */
+  uint32_t column;         /* LogUp column of the lookup program (boundary: 0) */
+  uint32_t fraction;       /* index within the column, program order (boundary: index in the statement's boundary list) */
+  uint64_t row;
+  uint64_t multiplicity[2];
+} mh_balance_push;
+/* Any set of lookup programs over their traces.  preprocessed: NULL, or per instance the raw preprocessed matrix (NULL where the
+ * program reads none).  randomness: EF pairs, at least as many as every program reads.  Boundary pushes: boundary_denoms = n_boundary
+ * EF pairs, boundary_signs = +1 / -1 each (the statement holds when sum_pushes m / d + sum_boundary sign / denom = 0). */
+int mh_check_balance(mh_ctx* ctx, int n, const mh_lookup* const* lookups, const mh_trace* const* traces,
+                     const mh_trace* const* preprocessed /* or NULL */, const uint64_t* randomness /* EF pairs */, size_t n_randomness,
+                     const uint64_t* boundary_denoms /* EF pairs */, const int32_t* boundary_signs, size_t n_boundary, int flags,
+                     mh_balance_entry* entries, size_t entry_cap, size_t* n_entries, mh_balance_push* pushes, size_t push_cap,
+                     size_t* n_pushes);
+/* The statements: the arguments and the debug challenges of mh_check_miden* / mh_check_precompile*.  Boundary pushes: the block-hash
+ * seed, the two deferred-root terms and one KernelRomInit per kernel digest (MidenMultiAir::eval_external); the fixed EcGroup / UintVal
+ * consumes of the session (`session_stack_residual`).  No state of mh_miden / mh_precompile is touched. */
+int mh_check_balance_miden(mh_ctx* ctx, const mh_miden* m, const uint64_t* core_rowmajor, int log_core, const uint64_t* chiplets_rowmajor,
+                           int log_chiplets, const uint64_t* poseidon2_rowmajor, int log_poseidon2, const uint64_t* public_values /* [32] */,
+                           const uint64_t* aux_inputs, size_t n_aux_inputs, int flags, mh_balance_entry* entries, size_t entry_cap,
+                           size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);
+int mh_check_balance_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* const traces[3], const uint64_t* public_values,
+                                  const uint64_t* aux_inputs, size_t n_aux_inputs, int flags, mh_balance_entry* entries, size_t entry_cap,
+                                  size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);
+int mh_check_balance_precompile(mh_ctx* ctx, mh_precompile* s, const uint64_t* const mains_rowmajor[MH_PRECOMPILE_NUM_AIRS],
+                                const int log_heights[MH_PRECOMPILE_NUM_AIRS], const uint64_t public_root[4], int flags,
+                                mh_balance_entry* entries, size_t entry_cap, size_t* n_entries, mh_balance_push* pushes, size_t push_cap,
+                                size_t* n_pushes);
+int mh_check_balance_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_trace* const traces[MH_PRECOMPILE_NUM_AIRS],
+                                       const uint64_t public_root[4], int flags, mh_balance_entry* entries, size_t entry_cap,
+                                       size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ EXPORTS = [
     "mh_miden_load", "mh_miden_free", "mh_prove_miden", "mh_prove_miden_traces", "mh_verify_miden", "mh_miden_pcs_params",
     "mh_miden_challenger_state", "mh_miden_hash_kernel_digests", "mh_miden_pre_observe", "mh_miden_eval_external", "mh_miden_air_blob",
     "mh_check_constraints", "mh_check_miden", "mh_check_miden_traces", "mh_check_precompile", "mh_check_precompile_traces",
+    "mh_check_balance", "mh_check_balance_miden", "mh_check_balance_miden_traces", "mh_check_balance_precompile", "mh_check_balance_precompile_traces",
 ]
 
 # the in-tree cache of precompiled constraint kernels (filled by __graft_entry__.build() / tools/jit_precompile.py); $MH_JIT_CACHE_DIR wins
@@ -89,6 +90,95 @@ def _run_check(ctx, call, cap=256):
         if n.value <= cap:
             return [out[i] for i in range(n.value)]
         cap = n.value
+
+
+# ---- bus balance (include/midenhip.h mh_check_balance*) ----
+MH_BALANCE_NO_PUSHES = (1 << 64) - 1  # BalanceEntry.first_push: the push list was not collected (more than 2^22 pushes)
+
+
+class BalancePush(C.Structure):
+    """mh_balance_push: a live push (the reference's PushRecord without msg_repr); instance -1 is a boundary push of the statement."""
+    _fields_ = [("instance", C.c_int32), ("column", C.c_uint32), ("fraction", C.c_uint32), ("row", C.c_uint64),
+                ("multiplicity", C.c_uint64 * 2)]
+
+    def key(self):
+        return (self.instance, self.row, self.column, self.fraction, (self.multiplicity[0], self.multiplicity[1]))
+
+    def __eq__(self, other):
+        return isinstance(other, BalancePush) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return (f"BalancePush(instance={self.instance}, row={self.row}, column={self.column}, fraction={self.fraction}, "
+                f"multiplicity=({self.multiplicity[0]}, {self.multiplicity[1]}))")
+
+
+class BalanceEntry(C.Structure):
+    """mh_balance_entry: an encoded denominator whose net multiplicity is not zero (the reference's Unmatched).  `pushes` is the exact
+    number of live pushes on it; `push_list` (set by check_balance) holds them, or None when the push list was not collected."""
+    _fields_ = [("denom", C.c_uint64 * 2), ("net", C.c_uint64 * 2), ("pushes", C.c_uint64), ("first_push", C.c_uint64)]
+    push_list = None
+
+    def key(self):
+        return ((self.denom[0], self.denom[1]), (self.net[0], self.net[1]), self.pushes, self.first_push)
+
+    def __eq__(self, other):
+        return isinstance(other, BalanceEntry) and self.key() == other.key() and self.push_list == other.push_list
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return (f"BalanceEntry(denom=({self.denom[0]}, {self.denom[1]}), net=({self.net[0]}, {self.net[1]}), pushes={self.pushes}, "
+                f"first_push={self.first_push}, push_list={self.push_list})")
+
+
+def _run_balance(ctx, call, entry_cap=256, push_cap=1024):
+    """call(entries, entry_cap, n_entries_ptr, pushes, push_cap, n_pushes_ptr) -> rc; re-run with room for everything when a buffer was
+    short.  -> [BalanceEntry], each with its push_list."""
+    while True:
+        ent, psh = (BalanceEntry * max(1, entry_cap))(), (BalancePush * max(1, push_cap))()
+        ne, np_ = C.c_size_t(0), C.c_size_t(0)
+        rc = call(ent, C.c_size_t(entry_cap), C.byref(ne), psh, C.c_size_t(push_cap), C.byref(np_))
+        if rc not in (0, MH_ERR_UNSATISFIED):
+            ctx.check(rc)
+        collected = ne.value == 0 or ent[0].first_push != MH_BALANCE_NO_PUSHES
+        if ne.value <= entry_cap and (np_.value <= push_cap or not collected):
+            out = []
+            for i in range(ne.value):
+                e = BalanceEntry.from_buffer_copy(ent[i])
+                e.push_list = [BalancePush.from_buffer_copy(psh[e.first_push + k]) for k in range(e.pushes)] if collected else None
+                out.append(e)
+            return out
+        entry_cap, push_cap = max(entry_cap, ne.value), max(push_cap, np_.value if collected else 0)
+
+
+def check_balance(ctx, lookups, traces, randomness, boundary=(), preprocessed=None, exact=False):
+    """mh_check_balance: net the live pushes of the DeviceLookup programs `lookups` over `traces` (Trace objects or host matrices) under
+    the challenges `randomness` (EF pairs), plus the boundary pushes `boundary` = [((c0, c1), +1 | -1)].  preprocessed: None, or per
+    instance the raw preprocessed matrix (or None).  -> [BalanceEntry] ascending by denominator, each with its push_list; [] when the
+    buses balance.  exact=True skips the sum screen."""
+    lib = ctx.lib
+    n = len(lookups)
+    if len(traces) != n or (preprocessed is not None and len(preprocessed) != n):
+        raise MidenHipError("check_balance: one trace (and one preprocessed matrix or None) per lookup program expected")
+    tr = [_as_trace(ctx, t) for t in traces]
+    pr = [_as_trace(ctx, t) for t in (preprocessed if preprocessed is not None else [None] * n)]
+    la = (C.c_void_p * max(1, n))(*[l.h for l in lookups])
+    ta = (C.c_void_p * max(1, n))(*[t.h for t in tr])
+    pa = (C.c_void_p * max(1, n))(*[t.h if t is not None else None for t in pr])
+    rnd = _arr([int(x) for r in randomness for x in r] or [0])
+    bd = _arr([int(x) for d, _ in boundary for x in d] or [0])
+    bs = np.ascontiguousarray([int(s) for _, s in boundary] or [0], dtype=np.int32)
+    flags = C.c_int(MH_CHECK_EXACT if exact else 0)
+
+    def call(ent, ecap, ne, psh, pcap, np_):
+        return lib.mh_check_balance(ctx.h, C.c_int(n), la, ta, pa, _ptr(rnd), C.c_size_t(len(randomness)), _ptr(bd),
+                                    bs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(len(boundary)), flags, ent, ecap, ne, psh, pcap, np_)
+
+    return _run_balance(ctx, call)
 
 
 def load_library():
@@ -839,6 +929,26 @@ class Miden:
                                                           flags, out, cap, n)
         return _run_check(self.ctx, call)
 
+    def check_balance(self, core, chiplets, poseidon2, public_values, aux_inputs, exact=False):
+        """mh_check_balance_miden(_traces): the unmatched bus messages of this statement under check()'s challenges -> [BalanceEntry]
+        ([] when the buses balance); host row-major matrices or Trace objects."""
+        lib, mats = self.ctx.lib, (core, chiplets, poseidon2)
+        pv, aux = _arr([int(x) for x in public_values]), _arr([int(x) for x in aux_inputs] or [0])
+        flags = C.c_int(MH_CHECK_EXACT if exact else 0)
+        if all(isinstance(m, Trace) for m in mats):
+            tr = (C.c_void_p * 3)(*[m.h for m in mats])
+            call = lambda *out: lib.mh_check_balance_miden_traces(self.ctx.h, self.h, tr, _ptr(pv), _ptr(aux), C.c_size_t(len(aux_inputs)),
+                                                                  flags, *out)
+        else:
+            hs = [np.ascontiguousarray(m, dtype=np.uint64) for m in mats]
+            lg = [int(m.shape[0]).bit_length() - 1 for m in hs]
+            if [m.shape[1] for m in hs] != [51, 22, 16] or any(m.shape[0] != 1 << l for m, l in zip(hs, lg)):
+                raise MidenHipError("Miden.check_balance: widths 51 / 22 / 16 and power-of-two heights expected")
+            call = lambda *out: lib.mh_check_balance_miden(self.ctx.h, self.h, _ptr(hs[0]), C.c_int(lg[0]), _ptr(hs[1]), C.c_int(lg[1]),
+                                                           _ptr(hs[2]), C.c_int(lg[2]), _ptr(pv), _ptr(aux), C.c_size_t(len(aux_inputs)),
+                                                           flags, *out)
+        return _run_balance(self.ctx, call)
+
     def free(self):
         if getattr(self, "h", None) and self.ctx.h:
             self.ctx.lib.mh_miden_free(self.h)
@@ -918,6 +1028,27 @@ class Precompile:
             lh = (C.c_int * 12)(*lg)
             call = lambda out, cap, n: lib.mh_check_precompile(self.ctx.h, self.h, ptrs, lh, _ptr(root), flags, out, cap, n)
         return _run_check(self.ctx, call)
+
+    def check_balance(self, mains, public_root, exact=False):
+        """mh_check_balance_precompile(_traces): the unmatched bus messages of the session under check()'s challenges -> [BalanceEntry]
+        ([] when the buses balance)."""
+        lib = self.ctx.lib
+        if len(mains) != 12:
+            raise MidenHipError("Precompile.check_balance: twelve main traces expected")
+        root = _arr([int(x) for x in public_root])
+        flags = C.c_int(MH_CHECK_EXACT if exact else 0)
+        if all(isinstance(m, Trace) for m in mains):
+            tr = (C.c_void_p * 12)(*[m.h for m in mains])
+            call = lambda *out: lib.mh_check_balance_precompile_traces(self.ctx.h, self.h, tr, _ptr(root), flags, *out)
+        else:
+            hs = [np.ascontiguousarray(m, dtype=np.uint64) for m in mains]
+            lg = [int(m.shape[0]).bit_length() - 1 for m in hs]
+            if tuple(m.shape[1] for m in hs) != self.WIDTHS or any(m.shape[0] != 1 << l for m, l in zip(hs, lg)):
+                raise MidenHipError("Precompile.check_balance: the AIRs' widths and power-of-two heights expected")
+            ptrs = (u64p * 12)(*[_ptr(m) for m in hs])
+            lh = (C.c_int * 12)(*lg)
+            call = lambda *out: lib.mh_check_balance_precompile(self.ctx.h, self.h, ptrs, lh, _ptr(root), flags, *out)
+        return _run_balance(self.ctx, call)
 
     def free(self):
         if getattr(self, "h", None) and self.ctx.h:

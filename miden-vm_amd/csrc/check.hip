@@ -201,7 +201,7 @@ __global__ __launch_bounds__(CT) void k_compact_write(const u32* __restrict__ fl
 }
 
 // flags [n] -> rows [n] (ascending); returns their number (waits for the stream)
-static size_t compact_rows(mh_ctx* c, const u32* flags, size_t n, u64* rows) {
+size_t compact_rows(mh_ctx* c, const u32* flags, size_t n, u64* rows) {
   const size_t tiles = (n + CTILE - 1) / CTILE;
   DevBuf cnt(tiles * 8), total(8);
   MH_LAUNCH(k_compact_count, dim3((unsigned)tiles), dim3(CT), 0, c->stream, flags, n, cnt.u());
@@ -374,6 +374,20 @@ static int report(mh_ctx* c, std::vector<mh_check_entry>& e, const char* const* 
   return MH_ERR_UNSATISFIED;
 }
 
+// debug challenges of a statement: the transcript of a proof up to the main commitment, which is left out
+std::vector<e2> debug_challenges(const u64 challenger_state[12], const u64* pre_observe, size_t n_pre, int n_airs, mh_trace* const* traces,
+                                 size_t count) {
+  HostChallenger ch;
+  ch.hash = MH_LMCS_POSEIDON2;
+  ch.init_from_state(challenger_state);
+  for (size_t i = 0; i < n_pre; i++) ch.observe_framing(pre_observe[i]);
+  ch.observe((u64)n_airs);
+  for (int i = 0; i < n_airs; i++) ch.observe((u64)traces[i]->log_n);
+  std::vector<e2> rnd;
+  for (size_t i = 0; i < count; i++) rnd.push_back(ch.sample_ef());
+  return rnd;
+}
+
 int check_statement(mh_ctx* c, int n_airs, mh_air* const* airs, mh_trace* const* traces, const mh_trace* const* preps, const u64* publics,
                     size_t n_publics, const u64 challenger_state[12], const u64* pre_observe, size_t n_pre, mh_external_assertions ext,
                     void* ext_user, const char* const* names, int flags, mh_check_entry* out, size_t cap, size_t* n_entries) {
@@ -391,15 +405,7 @@ int check_statement(mh_ctx* c, int n_airs, mh_air* const* airs, mh_trace* const*
       MH_REQUIRE(!airs[i]->aux_width || airs[i]->lookup, "an AIR with aux columns needs its lookup program attached");
       max_rand = std::max(max_rand, airs[i]->num_randomness);
     }
-    // debug challenges: the transcript of a proof up to the main commitment, which is left out
-    HostChallenger ch;
-    ch.hash = MH_LMCS_POSEIDON2;
-    ch.init_from_state(challenger_state);
-    for (size_t i = 0; i < n_pre; i++) ch.observe_framing(pre_observe[i]);
-    ch.observe((u64)n_airs);
-    for (int i = 0; i < n_airs; i++) ch.observe((u64)traces[i]->log_n);
-    std::vector<e2> rnd;
-    for (size_t i = 0; i < max_rand; i++) rnd.push_back(ch.sample_ef());
+    const std::vector<e2> rnd = debug_challenges(challenger_state, pre_observe, n_pre, n_airs, traces, max_rand);
     // aux traces on the device, the statement's aux values
     std::vector<std::unique_ptr<mh_trace>> aux(n_airs);
     std::vector<std::vector<e2>> aux_vals(n_airs);

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/midenhip.h"
 #include "ctx.hpp"
+#include <functional>
 #include <vector>
 
 // ---- ntt.hip ---------------------------------------------------------------------------------
@@ -176,6 +177,8 @@ u64 fri_grind_bytes(mh_ctx* c, int lmcs, const std::vector<uint8_t>& prefix, int
 struct mh_lookup;
 mh_trace* lookup_build_aux(mh_ctx* c, const mh_lookup* lk, const mh_trace* main, const mh_trace* prep, const std::vector<e2>& randomness,
                            e2* acc_final);
+// the planes the compiled lookup program writes, [2 * n_out][n]: what lookup_build_aux sums and balance.hip nets (enqueued, no wait)
+void lookup_planes(mh_ctx* c, const mh_lookup* lk, const mh_trace* main, const mh_trace* prep, const std::vector<e2>& randomness, DevBuf& planes);
 
 // quotient.hip: the screen of the constraint checker -- the AIR's constraint program on the trace domain, alpha-folded into acc [2][n]
 void constraint_fold_trace_domain(mh_ctx* c, const mh_air* air, const mh_trace* main, const mh_trace* aux, const mh_trace* prep,
@@ -187,3 +190,24 @@ void constraint_fold_trace_domain(mh_ctx* c, const mh_air* air, const mh_trace* 
 int check_statement(mh_ctx* c, int n_airs, mh_air* const* airs, mh_trace* const* traces, const mh_trace* const* preps, const u64* publics,
                     size_t n_publics, const u64 challenger_state[12], const u64* pre_observe, size_t n_pre, mh_external_assertions ext,
                     void* ext_user, const char* const* names, int flags, mh_check_entry* out, size_t cap, size_t* n_entries);
+// the statement's debug challenges (shared with balance.hip: a balance report and a constraint report refer to the same challenges)
+std::vector<e2> debug_challenges(const u64 challenger_state[12], const u64* pre_observe, size_t n_pre, int n_airs, mh_trace* const* traces,
+                                 size_t count);
+// flags [n] -> rows [n] (ascending indices of the non-zero flags); returns their number (waits for the stream)
+size_t compact_rows(mh_ctx* c, const u32* flags, size_t n, u64* rows);
+
+// ---- balance.hip: unmatched LogUp bus messages (mh_check_balance*) ------------------------------------------------------------------
+// A boundary push of a statement: the encoded denominator and its multiplicity +1 / -1.  The statements' eval_external sums the same
+// lists (csrc/miden.cpp, csrc/verifier.cpp), so the external assertion and the balance report cannot drift apart.
+struct BoundaryPush {
+  e2 denom;
+  int sign;
+};
+// verifier.cpp: the fixed `EcGroup` / `UintVal` consumes of the precompile session under (alpha, beta); false: a denominator is zero
+bool precompile_session_boundary(bool fixed_uints, e2 alpha, e2 beta, std::vector<BoundaryPush>& out);
+// the balance check of one statement with the challenges of check_statement; `boundary(rnd, out)` returns false on a malformed statement
+// or a zero denominator.  Never throws.
+int balance_statement(mh_ctx* c, int n_airs, mh_air* const* airs, mh_trace* const* traces, const mh_trace* const* preps,
+                      const u64 challenger_state[12], const u64* pre_observe, size_t n_pre,
+                      const std::function<bool(const std::vector<e2>&, std::vector<BoundaryPush>&)>& boundary, const char* const* names, int flags,
+                      mh_balance_entry* entries, size_t entry_cap, size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);

@@ -252,20 +252,20 @@ __global__ __launch_bounds__(256) void k_reg_build(RegBuildArgs a) {
   a.b1[i] = acc.c1;
 }
 
-// Build the aux trace of `lk` over `main` with the lookup challenges `randomness` (EF pairs).
-mh_trace* lookup_build_aux(mh_ctx* c, const mh_lookup* lk, const mh_trace* main, const mh_trace* prep, const std::vector<e2>& randomness,
-                           e2* acc_final) {
+// The compiled lookup program of `lk` over `main`: every output (m_j, d_j per fraction, then the registers' keep / build / coefficients) as
+// a pair of planes [2 * n_out][n] in `planes` (c0, c1; the c1 plane of a base-field output is not written).  Enqueued on c->stream, no
+// wait.  Shared by the aux builder below and the bus-balance checker (balance.hip).
+void lookup_planes(mh_ctx* c, const mh_lookup* lk, const mh_trace* main, const mh_trace* prep, const std::vector<e2>& randomness, DevBuf& planes) {
   MH_REQUIRE(main->width == lk->main_width, "lookup program was exported for a different trace width");
   MH_REQUIRE(!lk->preprocessed_width || (prep && prep->width == lk->preprocessed_width && prep->log_n == main->log_n),
              "lookup program reads preprocessed columns: the preprocessed matrix (same height as the trace) is required");
   MH_REQUIRE(randomness.size() >= lk->num_randomness, "not enough lookup challenges");
   const int log_n = main->log_n;
   const size_t n = (size_t)1 << log_n;
-  const size_t K = lk->n_fractions();
   size_t pm = 0;
   for (auto& col : lk->periodic) pm = std::max(pm, col.size());
   MH_REQUIRE(pm <= n, "trace shorter than a periodic column");
-  // small tables: periodic columns tiled to the longest period, challenges, per-column counts, output kinds
+  // small tables: periodic columns tiled to the longest period, challenges
   std::vector<u64> blob;
   const size_t prow = pm ? pm : 1;
   for (auto& col : lk->periodic)
@@ -276,16 +276,11 @@ mh_trace* lookup_build_aux(mh_ctx* c, const mh_lookup* lk, const mh_trace* main,
     blob.push_back(i < randomness.size() ? randomness[i].c1 : 0);
   }
   if (blob.empty()) blob.push_back(0);
-  DevBuf dblob(blob.size() * 8), dcount(lk->col_count.size() * 4), dext(lk->out_ext.size()), derr(4);
+  DevBuf dblob(blob.size() * 8);  // goes back to the pool on return: reuse is ordered on the stream behind the program's reads
   c->h2d(dblob.p, blob.data(), blob.size() * 8);
-  c->h2d(dcount.p, lk->col_count.data(), lk->col_count.size() * 4);
-  c->h2d(dext.p, lk->out_ext.data(), lk->out_ext.size());
-  HIP_CHECK(hipMemsetAsync(derr.p, 0, 4, c->stream));
-
   trace_wait_ready(c, main);
   trace_wait_ready(c, prep);
-  const size_t n_out = lk->out_ext.size();
-  DevBuf planes(2 * n_out * n * 8);  // outputs m_j, d_j, then the registers' keep / build / coefficients: two planes each
+  planes.alloc(2 * lk->out_ext.size() * n * 8);
   JitArgs j{};
   j.main_lde = main->cols.u();  // the trace itself: one "coset", B = 1
   j.aux_lde = main->cols.u();   // never read (a lookup program has no aux inputs)
@@ -297,6 +292,21 @@ mh_trace* lookup_build_aux(mh_ctx* c, const mh_lookup* lk, const mh_trace* main,
   j.inv_first = dblob.u(); j.inv_last = dblob.u();
   j.randomness = dblob.u() + o_rnd;
   j.log_n = log_n;  // log_cosets = log_d = log_dl = jc_shift = t0 = 0: point q IS row r
+  jit_quotient_run(c, lk->jit, j, n);
+}
+
+// Build the aux trace of `lk` over `main` with the lookup challenges `randomness` (EF pairs).
+mh_trace* lookup_build_aux(mh_ctx* c, const mh_lookup* lk, const mh_trace* main, const mh_trace* prep, const std::vector<e2>& randomness,
+                           e2* acc_final) {
+  const int log_n = main->log_n;
+  const size_t n = (size_t)1 << log_n;
+  const size_t K = lk->n_fractions();
+  DevBuf dcount(lk->col_count.size() * 4), dext(lk->out_ext.size()), derr(4);
+  DevBuf planes;  // outputs m_j, d_j, then the registers' keep / build / coefficients: two planes each
+  MH_REQUIRE(main->width == lk->main_width, "lookup program was exported for a different trace width");
+  c->h2d(dcount.p, lk->col_count.data(), lk->col_count.size() * 4);
+  c->h2d(dext.p, lk->out_ext.data(), lk->out_ext.size());
+  HIP_CHECK(hipMemsetAsync(derr.p, 0, 4, c->stream));
   std::unique_ptr<mh_trace> aux(new mh_trace());
   aux->ctx = c; aux->log_n = log_n; aux->width = 2 * lk->num_aux_cols();
   aux->cols.alloc(aux->width * n * 8);
@@ -305,7 +315,7 @@ mh_trace* lookup_build_aux(mh_ctx* c, const mh_lookup* lk, const mh_trace* main,
   DevBuf tile_sums(2 * tiles * 8), grand(2 * 8);
   {
     ProfScope ps(c, "logup_aux", (double)n * (24.0 * K + 16.0 * lk->num_cols + 8.0 * lk->main_width));
-    jit_quotient_run(c, lk->jit, j, n);
+    lookup_planes(c, lk, main, prep, randomness, planes);
     LogupArgs a{};
     a.planes = planes.u(); a.col_count = (const u32*)dcount.p; a.out_ext = (const unsigned char*)dext.p;
     a.num_cols = (u32)lk->num_cols; a.log_n = log_n; a.aux = aux->cols.u(); a.totals = totals.u(); a.err = (u32*)derr.p;

@@ -95,6 +95,26 @@ struct Challenges {  // air/src/lookup/challenges.rs:14-36
   }
 };
 
+// The statement's boundary pushes (MidenAir::boundary_correction over emit_core_boundary / emit_chiplets_boundary) as (denominator, sign):
+// the list eval_external sums and mh_check_balance_miden* nets.  false: a denominator is zero (the reference's ReductionError).
+bool boundary_pushes(const Challenges& ch, const u64* aux_inputs, size_t n_aux, std::vector<BoundaryPush>& out) {
+  bool zero_den = false;
+  auto push = [&](e2 d, int sign) {
+    if (e2_is_zero(d)) { zero_den = true; return; }
+    out.push_back(BoundaryPush{d, sign});
+  };
+  // Core (emit_core_boundary): the block-hash seed Child{parent 0, program_hash, is_first_child 0, is_loop_body 0}; the deferred-root
+  // log's initial entry added, its final entry removed
+  u64 seed[7] = {aux_inputs[0], aux_inputs[1], aux_inputs[2], aux_inputs[3], 0, 0, 0};
+  push(ch.encode(BUS_BLOCK_HASH_TABLE, seed, 7), 1);
+  const u64 zero4[4] = {0, 0, 0, 0};
+  push(ch.encode(BUS_LOG_DEFERRED_ROOT, zero4, 4), 1);
+  push(ch.encode(BUS_LOG_DEFERRED_ROOT, aux_inputs + AUX_DEFERRED_ROOT, 4), -1);
+  // Chiplets (emit_chiplets_boundary): one KernelRomInit per kernel digest; Poseidon2Permutation: nothing
+  for (size_t i = AUX_KERNEL_DIGESTS; i < n_aux; i += 4) push(ch.encode(BUS_KERNEL_ROM_INIT, aux_inputs + i, 4), 1);
+  return !zero_den;
+}
+
 // -> 0 ok, -1 a denominator is zero (the reference's ReductionError), -2 shape error
 int eval_external(const u64* rnd, size_t n_rnd, const u64* aux_inputs, size_t n_aux, const u64* const* aux_values, const size_t* n_aux_values,
                   int n_airs, u64 out[2]) {
@@ -102,23 +122,13 @@ int eval_external(const u64* rnd, size_t n_rnd, const u64* aux_inputs, size_t n_
       (n_aux - AUX_KERNEL_DIGESTS) % 4)
     return -2;
   const Challenges ch(e2{gl_canon(rnd[0]), gl_canon(rnd[1])}, e2{gl_canon(rnd[2]), gl_canon(rnd[3])});
+  std::vector<BoundaryPush> pushes;
+  if (!boundary_pushes(ch, aux_inputs, n_aux, pushes)) return -1;
   e2 total = e2_make(0);
-  bool zero_den = false;
-  auto add_inv = [&](e2 d, bool negate) {
-    if (e2_is_zero(d)) { zero_den = true; return; }
-    const e2 v = e2_inv(d);
-    total = negate ? e2_sub(total, v) : e2_add(total, v);
-  };
-  // Core (emit_core_boundary): the block-hash seed Child{parent 0, program_hash, is_first_child 0, is_loop_body 0}; the deferred-root
-  // log's initial entry added, its final entry removed
-  u64 seed[7] = {aux_inputs[0], aux_inputs[1], aux_inputs[2], aux_inputs[3], 0, 0, 0};
-  add_inv(ch.encode(BUS_BLOCK_HASH_TABLE, seed, 7), false);
-  const u64 zero4[4] = {0, 0, 0, 0};
-  add_inv(ch.encode(BUS_LOG_DEFERRED_ROOT, zero4, 4), false);
-  add_inv(ch.encode(BUS_LOG_DEFERRED_ROOT, aux_inputs + AUX_DEFERRED_ROOT, 4), true);
-  // Chiplets (emit_chiplets_boundary): one KernelRomInit per kernel digest; Poseidon2Permutation: nothing
-  for (size_t i = AUX_KERNEL_DIGESTS; i < n_aux; i += 4) add_inv(ch.encode(BUS_KERNEL_ROM_INIT, aux_inputs + i, 4), false);
-  if (zero_den) return -1;
+  for (const BoundaryPush& p : pushes) {
+    const e2 v = e2_inv(p.denom);
+    total = p.sign < 0 ? e2_sub(total, v) : e2_add(total, v);
+  }
   for (int a = 0; a < 3; a++) {
     if (n_aux_values[a] != 1) return -2;  // every Miden AIR commits exactly one LogUp final
     total = e2_add(total, e2{gl_canon(aux_values[a][0]), gl_canon(aux_values[a][1])});
@@ -332,6 +342,56 @@ int mh_check_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* const traces
                           size_t n_aux_inputs, int flags, mh_check_entry* out, size_t cap, size_t* n_entries) {
   if (!traces) return MH_ERR_INVALID;
   return check_common(ctx, m, traces, public_values, aux_inputs, n_aux_inputs, flags, out, cap, n_entries);
+}
+
+// the bus balance of this statement (balance.hip) with check_common's challenges and eval_external's boundary pushes
+static int balance_common(mh_ctx* ctx, const mh_miden* m, mh_trace* const* traces, const uint64_t* public_values, const uint64_t* aux_inputs,
+                          size_t n_aux_inputs, int flags, mh_balance_entry* entries, size_t entry_cap, size_t* n_entries, mh_balance_push* pushes,
+                          size_t push_cap, size_t* n_pushes) {
+  if (!ctx || !m || m->ctx != ctx || !n_entries || !n_pushes) return MH_ERR_INVALID;
+  mh_pcs_params prm;
+  mh_miden_pcs_params(&prm);
+  u64 pre[MH_MIDEN_PRE_OBSERVE_FELTS], state[12];
+  if (mh_miden_pre_observe(&prm, public_values, aux_inputs, n_aux_inputs, pre) != MH_OK) {
+    ctx->err = "mh_check_balance_miden: 32 public values and aux inputs = program hash (4) | deferred root (4) | kernel digests (4 each, <= 255) expected";
+    return MH_ERR_INVALID;
+  }
+  mh_miden_challenger_state(state);
+  static const char* const names[3] = {"core", "chiplets", "poseidon2"};
+  auto boundary = [&](const std::vector<e2>& rnd, std::vector<BoundaryPush>& out) {
+    return rnd.size() >= 2 && boundary_pushes(Challenges(rnd[0], rnd[1]), aux_inputs, n_aux_inputs, out);
+  };
+  return balance_statement(ctx, 3, m->airs, traces, nullptr, state, pre, MH_MIDEN_PRE_OBSERVE_FELTS, boundary, names, flags, entries, entry_cap,
+                           n_entries, pushes, push_cap, n_pushes);
+}
+
+int mh_check_balance_miden(mh_ctx* ctx, const mh_miden* m, const uint64_t* core_rowmajor, int log_core, const uint64_t* chiplets_rowmajor,
+                           int log_chiplets, const uint64_t* poseidon2_rowmajor, int log_poseidon2, const uint64_t* public_values,
+                           const uint64_t* aux_inputs, size_t n_aux_inputs, int flags, mh_balance_entry* entries, size_t entry_cap,
+                           size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes) {
+  if (!ctx || !m || m->ctx != ctx) return MH_ERR_INVALID;
+  const uint64_t* rm[3] = {core_rowmajor, chiplets_rowmajor, poseidon2_rowmajor};
+  const int lh[3] = {log_core, log_chiplets, log_poseidon2};
+  mh_trace* tr[3] = {nullptr, nullptr, nullptr};
+  int rc = MH_OK;
+  for (int i = 0; i < 3 && rc == MH_OK; i++) {
+    if (!rm[i] || lh[i] < 1 || lh[i] > 30) {
+      ctx->err = "mh_check_balance_miden: null matrix or log height outside 1..30";
+      rc = MH_ERR_INVALID;
+    } else {
+      rc = mh_trace_upload(ctx, rm[i], lh[i], m->airs[i]->main_width, &tr[i]);
+    }
+  }
+  if (rc == MH_OK)
+    rc = balance_common(ctx, m, tr, public_values, aux_inputs, n_aux_inputs, flags, entries, entry_cap, n_entries, pushes, push_cap, n_pushes);
+  for (mh_trace* t : tr) mh_trace_free(t);
+  return rc;
+}
+int mh_check_balance_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* const traces[3], const uint64_t* public_values,
+                                  const uint64_t* aux_inputs, size_t n_aux_inputs, int flags, mh_balance_entry* entries, size_t entry_cap,
+                                  size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes) {
+  if (!traces) return MH_ERR_INVALID;
+  return balance_common(ctx, m, traces, public_values, aux_inputs, n_aux_inputs, flags, entries, entry_cap, n_entries, pushes, push_cap, n_pushes);
 }
 
 }  // extern "C"

@@ -287,4 +287,51 @@ int mh_check_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_trace* const tr
   return check_common(ctx, s, traces, public_root, flags, out, cap, n_entries);
 }
 
+// the bus balance of the session (balance.hip; bus_balance.rs:25-108) with check_common's challenges and the verifier's fixed consumes
+static int balance_common(mh_ctx* ctx, mh_precompile* s, mh_trace* const* traces, const uint64_t* public_root, int flags, mh_balance_entry* entries,
+                          size_t entry_cap, size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes) {
+  if (!ctx || !s || s->ctx != ctx || !public_root || !n_entries || !n_pushes) return MH_ERR_INVALID;
+  mh_pcs_params prm;
+  mh_precompile_pcs_params(&prm);
+  u64 pre[MH_PRECOMPILE_PRE_OBSERVE_FELTS], state[12] = {0};
+  const u64 no_root[4] = {0, 0, 0, 0};
+  int rc = mh_precompile_pre_observe(&prm, no_root, public_root, pre);
+  if (rc != MH_OK) return rc;
+  const mh_trace* preps[N_AIRS] = {};
+  preps[BYTE_PAIR_LUT] = s->table;  // the raw table: the AIR's attachment (made by the provers) is not touched
+  static const char* const names[N_AIRS] = {"chunk_node", "poseidon2", "keccak_round", "byte_pair_lut", "keccak_sponge", "transcript_eval",
+                                            "uint_store_mul", "uint_add", "ec_groups", "ec_point_store", "ec_group_add", "ec_msm"};
+  auto boundary = [](const std::vector<e2>& rnd, std::vector<BoundaryPush>& out) {
+    return rnd.size() >= 2 && precompile_session_boundary(true, rnd[0], rnd[1], out);
+  };
+  return balance_statement(ctx, N_AIRS, s->airs, traces, preps, state, pre, MH_PRECOMPILE_PRE_OBSERVE_FELTS, boundary, names, flags, entries,
+                           entry_cap, n_entries, pushes, push_cap, n_pushes);
+}
+
+int mh_check_balance_precompile(mh_ctx* ctx, mh_precompile* s, const uint64_t* const mains_rowmajor[MH_PRECOMPILE_NUM_AIRS],
+                                const int log_heights[MH_PRECOMPILE_NUM_AIRS], const uint64_t public_root[4], int flags,
+                                mh_balance_entry* entries, size_t entry_cap, size_t* n_entries, mh_balance_push* pushes, size_t push_cap,
+                                size_t* n_pushes) {
+  if (!ctx || !s || s->ctx != ctx || !mains_rowmajor || !log_heights) return MH_ERR_INVALID;
+  mh_trace* tr[N_AIRS] = {};
+  int rc = MH_OK;
+  for (int i = 0; i < N_AIRS && rc == MH_OK; i++) {
+    if (!mains_rowmajor[i] || log_heights[i] < 1 || log_heights[i] > 30) {
+      ctx->err = "mh_check_balance_precompile: null matrix or log height outside 1..30";
+      rc = MH_ERR_INVALID;
+    } else {
+      rc = mh_trace_upload(ctx, mains_rowmajor[i], log_heights[i], s->airs[i]->main_width, &tr[i]);
+    }
+  }
+  if (rc == MH_OK) rc = balance_common(ctx, s, tr, public_root, flags, entries, entry_cap, n_entries, pushes, push_cap, n_pushes);
+  for (mh_trace* t : tr) mh_trace_free(t);
+  return rc;
+}
+int mh_check_balance_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_trace* const traces[MH_PRECOMPILE_NUM_AIRS],
+                                       const uint64_t public_root[4], int flags, mh_balance_entry* entries, size_t entry_cap,
+                                       size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes) {
+  if (!traces) return MH_ERR_INVALID;
+  return balance_common(ctx, s, traces, public_root, flags, entries, entry_cap, n_entries, pushes, push_cap, n_pushes);
+}
+
 }  // extern "C"

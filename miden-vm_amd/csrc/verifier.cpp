@@ -11,6 +11,7 @@
 #include "air.hpp"
 #include "challenger.hpp"
 #include "gl.cuh"
+#include "kernels.hpp"
 #include <algorithm>
 #include <cstring>
 #include <numeric>
@@ -686,11 +687,9 @@ int mh_external_logup_balance(void* user, const uint64_t* randomness, size_t n_r
 // `mh_external_precompile_session` is the whole correction -- what the reference's verifier checks; the reduced form the smaller
 // test statements need (those that leave the uint store out: the EcGroup part only) is a callback of its own name,
 // `mh_external_precompile_session_ec_only`, so that no flag passed by mistake weakens the real one.
-static int precompile_session_external(bool fixed_uints, const uint64_t* randomness, size_t n_randomness, const uint64_t* const* aux_values,
-                                       const size_t* n_aux_values, int n_airs, uint64_t* assertions_out, size_t cap) {
-  if (!assertions_out || cap < 1 || n_airs < 0 || n_randomness < 2 || !randomness || (n_airs && (!aux_values || !n_aux_values))) return -1;
-  for (int i = 0; i < n_airs; i++)
-    if (n_aux_values[i] != 1 || !aux_values[i]) return -1;
+}  // extern "C"
+// the verifier's fixed consumes as (denominator, +1) pushes: the list `precompile_session_external` sums and mh_check_balance_precompile* nets
+bool precompile_session_boundary(bool fixed_uints, e2 alpha, e2 beta, std::vector<BoundaryPush>& out) {
   static const int MAX_MESSAGE_WIDTH = 18, BUS_UINT_VAL = 10, BUS_EC_GROUP = 14;
   static const u64 U256_BOUND_PTR = 1, K1_BASE_BOUND_PTR = 2, K1_SCALAR_BOUND_PTR = 3, K1_A_PTR = 8, K1_B_PTR = 9, K1_GROUP_PTR = 1;
   struct FixedUint {
@@ -702,12 +701,9 @@ static int precompile_session_external(bool fixed_uints, const uint64_t* randomn
       {K1_SCALAR_BOUND_PTR, K1_SCALAR_BOUND_PTR, {0xD0364140u, 0xBFD25E8Cu, 0xAF48A03Bu, 0xBAAEDCE6u, 0xFFFFFFFEu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}},
       {K1_A_PTR, K1_BASE_BOUND_PTR, {0, 0, 0, 0, 0, 0, 0, 0}},
       {K1_B_PTR, K1_BASE_BOUND_PTR, {7, 0, 0, 0, 0, 0, 0, 0}}};
-  const e2 alpha = e2{gl_canon(randomness[0]), gl_canon(randomness[1])}, beta = e2{gl_canon(randomness[2]), gl_canon(randomness[3])};
   e2 bp[MAX_MESSAGE_WIDTH + 1];
   bp[0] = e2_make(1);
   for (int i = 1; i <= MAX_MESSAGE_WIDTH; i++) bp[i] = e2_mul(bp[i - 1], beta);
-  e2 acc = e2_make(0);
-  for (int i = 0; i < n_airs; i++) acc = e2_add(acc, e2{gl_canon(aux_values[i][0]), gl_canon(aux_values[i][1])});
   bool zero_denominator = false;
   auto consume = [&](int bus, const u64* fields, int n) {
     e2 d = e2_add(alpha, e2_mulf(bp[MAX_MESSAGE_WIDTH], (u64)(bus + 1)));
@@ -716,7 +712,7 @@ static int precompile_session_external(bool fixed_uints, const uint64_t* randomn
       zero_denominator = true;
       return;
     }
-    acc = e2_add(acc, e2_inv(d));
+    out.push_back(BoundaryPush{d, 1});
   };
   const u64 k1_group[5] = {K1_GROUP_PTR, K1_A_PTR, K1_B_PTR, K1_BASE_BOUND_PTR, K1_SCALAR_BOUND_PTR};
   consume(BUS_EC_GROUP, k1_group, 5);
@@ -726,7 +722,20 @@ static int precompile_session_external(bool fixed_uints, const uint64_t* randomn
       for (int j = 0; j < 8; j++) f[2 + j] = u.limbs[j];
       consume(BUS_UINT_VAL, f, 10);
     }
-  if (zero_denominator) return -1;  // ReductionError: "fixed ... boundary denominator was zero"
+  return !zero_denominator;  // false: ReductionError "fixed ... boundary denominator was zero"
+}
+extern "C" {
+static int precompile_session_external(bool fixed_uints, const uint64_t* randomness, size_t n_randomness, const uint64_t* const* aux_values,
+                                       const size_t* n_aux_values, int n_airs, uint64_t* assertions_out, size_t cap) {
+  if (!assertions_out || cap < 1 || n_airs < 0 || n_randomness < 2 || !randomness || (n_airs && (!aux_values || !n_aux_values))) return -1;
+  for (int i = 0; i < n_airs; i++)
+    if (n_aux_values[i] != 1 || !aux_values[i]) return -1;
+  const e2 alpha = e2{gl_canon(randomness[0]), gl_canon(randomness[1])}, beta = e2{gl_canon(randomness[2]), gl_canon(randomness[3])};
+  e2 acc = e2_make(0);
+  for (int i = 0; i < n_airs; i++) acc = e2_add(acc, e2{gl_canon(aux_values[i][0]), gl_canon(aux_values[i][1])});
+  std::vector<BoundaryPush> pushes;
+  if (!precompile_session_boundary(fixed_uints, alpha, beta, pushes)) return -1;
+  for (const BoundaryPush& p : pushes) acc = e2_add(acc, e2_inv(p.denom));  // every fixed consume has sign +1
   assertions_out[0] = acc.c0;
   assertions_out[1] = acc.c1;
   return 1;
