@@ -110,6 +110,8 @@ pub const MH_LMCS_BLAKE3: c_int = 1;
 pub const MH_LMCS_KECCAK: c_int = 2;
 pub const MH_LMCS_RPO: c_int = 3;
 pub const MH_LMCS_RPX: c_int = 4;
+/// mh_ctx_set_salt: the largest salt width (felts per leaf) of the hiding LMCS
+pub const MH_MAX_SALT_ELEMS: c_int = 8;
 
 #[link(name = "midenhip")]
 unsafe extern "C" {
@@ -124,6 +126,9 @@ unsafe extern "C" {
     /// MH_LMCS_POSEIDON2 = 0, MH_LMCS_BLAKE3 = 1 (the hasher of mh_commit_traces / mh_tree_open on this context)
     pub fn mh_ctx_set_lmcs(ctx: *mut mh_ctx, lmcs: c_int) -> c_int;
     pub fn mh_ctx_get_lmcs(ctx: *const mh_ctx) -> c_int;
+    /// hiding LMCS (lmcs/hiding_config.rs): salt_elems = 0 (off) ..= 8; seed = [u64; 4], secret and fresh per proof, or null (OS entropy)
+    pub fn mh_ctx_set_salt(ctx: *mut mh_ctx, salt_elems: c_int, seed: *const u64) -> c_int;
+    pub fn mh_ctx_get_salt(ctx: *const mh_ctx) -> c_int;
     pub fn mh_blake3(data: *const u8, n: usize, out32: *mut u8);
     pub fn mh_prof_enable(ctx: *mut mh_ctx, on: c_int) -> c_int;
     pub fn mh_prof_filter(ctx: *mut mh_ctx, name: *const c_char) -> c_int;
@@ -152,6 +157,10 @@ unsafe extern "C" {
     pub fn mh_tree_open(ctx: *mut mh_ctx, t: *const mh_tree, indices: *const u64, n_idx: usize, alignment: usize, fields: *mut u64, n_fields: *mut usize, commits: *mut u64, n_commit_felts: *mut usize) -> c_int;
     pub fn mh_tree_download_lde(ctx: *mut mh_ctx, t: *const mh_tree, mat: c_int, out_rowmajor_bitrev: *mut u64) -> c_int;
     pub fn mh_tree_download_layers(ctx: *mut mh_ctx, t: *const mh_tree, out: *mut u64) -> c_int;
+    pub fn mh_tree_salt_elems(t: *const mh_tree) -> c_int;
+    pub fn mh_tree_salt_index(t: *const mh_tree) -> u64;
+    /// out = [2^log_height][salt_elems], physical (bit-reversed) row order
+    pub fn mh_tree_download_salt(ctx: *mut mh_ctx, t: *const mh_tree, out: *mut u64) -> c_int;
     pub fn mh_shard_commit_leaves(ctx: *mut mh_ctx, n_traces: c_int, traces: *const *mut mh_trace, log_blowup: c_int, rank: c_int, world: c_int, out: *mut *mut mh_shard) -> c_int;
     pub fn mh_shard_free(s: *mut mh_shard);
     pub fn mh_shard_leaf_digests(s: *mut mh_shard, n_digests: *mut usize) -> *mut u64;
@@ -196,6 +205,8 @@ unsafe extern "C" {
     pub fn mh_verify_ex(params: *const mh_pcs_params, n_airs: c_int, air_blobs: *const *const u64, air_blob_words: *const usize, log_trace_heights: *const u8, public_values: *const u64, n_public_values: usize, challenger_state: *const u64, pre_observe: *const u64, n_pre_observe: usize, fields: *const u64, n_fields: usize, commitments: *const u64, n_commitments: usize, preprocessed_root: *const u64, external: mh_external_assertions, external_user: *mut c_void, digest: *mut u64, err: *mut c_char, err_cap: usize) -> c_int;
     /// mh_verify_ex for MH_LMCS_RPO (3) / MH_LMCS_RPX (4) / MH_LMCS_POSEIDON2 (0)
     pub fn mh_verify_lmcs(lmcs: c_int, params: *const mh_pcs_params, n_airs: c_int, air_blobs: *const *const u64, air_blob_words: *const usize, log_trace_heights: *const u8, public_values: *const u64, n_public_values: usize, challenger_state: *const u64, pre_observe: *const u64, n_pre_observe: usize, fields: *const u64, n_fields: usize, commitments: *const u64, n_commitments: usize, preprocessed_root: *const u64, external: mh_external_assertions, external_user: *mut c_void, digest: *mut u64, err: *mut c_char, err_cap: usize) -> c_int;
+    /// mh_verify_lmcs for a proof made under a hiding LMCS (mh_ctx_set_salt): salt_elems salt felts follow every opened leaf
+    pub fn mh_verify_hiding(lmcs: c_int, salt_elems: c_int, params: *const mh_pcs_params, n_airs: c_int, air_blobs: *const *const u64, air_blob_words: *const usize, log_trace_heights: *const u8, public_values: *const u64, n_public_values: usize, challenger_state: *const u64, pre_observe: *const u64, n_pre_observe: usize, fields: *const u64, n_fields: usize, commitments: *const u64, n_commitments: usize, preprocessed_root: *const u64, external: mh_external_assertions, external_user: *mut c_void, digest: *mut u64, err: *mut c_char, err_cap: usize) -> c_int;
     pub fn mh_external_logup_balance(user: *mut c_void, randomness: *const u64, n_randomness: usize, aux_values: *const *const u64, n_aux_values: *const usize, log_trace_heights: *const u8, n_airs: c_int, assertions_out: *mut u64, cap: usize) -> c_int;
     pub fn mh_external_precompile_session(user: *mut c_void, randomness: *const u64, n_randomness: usize, aux_values: *const *const u64, n_aux_values: *const usize, log_trace_heights: *const u8, n_airs: c_int, assertions_out: *mut u64, cap: usize) -> c_int;
     pub fn mh_external_precompile_session_ec_only(user: *mut c_void, randomness: *const u64, n_randomness: usize, aux_values: *const *const u64, n_aux_values: *const usize, log_trace_heights: *const u8, n_airs: c_int, assertions_out: *mut u64, cap: usize) -> c_int;

@@ -126,6 +126,29 @@ void mh_host_free(void* p);
 #define MH_LMCS_RPX 4
 int mh_ctx_set_lmcs(mh_ctx* ctx, int lmcs);
 int mh_ctx_get_lmcs(const mh_ctx* ctx);
+/* Hiding LMCS: salted leaves (the reference's HidingLmcsConfig, crates/lifted-stark/src/lmcs/hiding_config.rs: LiftedMerkleTree with
+ * SALT_ELEMS > 0).  With salt_elems = n > 0 every tree the context commits from now on absorbs, after its last matrix, one more matrix
+ * of n columns and tree height (lifted_tree.rs:233-245), and every opened leaf hints its n raw salt felts, unpadded, after its aligned
+ * rows (lmcs/proof.rs:108-121).  It changes mh_commit_traces, mh_tree_open, mh_prove, mh_prove_host and the staged mh_session_* path;
+ * every tree of a proof is salted -- preprocessed (if committed on this context with the same setting), main, aux, quotient, each FRI
+ * round -- as the reference's prover uses one Lmcs for all of them.  Such a proof verifies with mh_verify_hiding; mh_verify,
+ * mh_verify_ex and mh_verify_lmcs are the non-hiding configurations.  salt_elems = 0 (the default) is the plain LMCS: same bytes, same
+ * kernels as a context that never called this.
+ * The salt is a PRF of the seed and is never stored: the salt row of PHYSICAL (bit-reversed, lifted_tree.rs:300-306) leaf row i of
+ * the t-th salted tree committed on the context since this call (t = 0, 1, ...; mh_tree_salt_index) is lanes 0 .. n-1 of one Poseidon2
+ * permutation of   [i, t, 0x53414c54, 0, 0, 0, 0, 0, seed0, seed1, seed2, seed3]   (seed words reduced mod p; the key sits in the
+ * capacity lanes), whichever hash function the LMCS uses.  The leaf kernels derive it in registers; mh_tree_open and
+ * mh_tree_download_salt regenerate the rows they need.  The same seed therefore reproduces the same trees and proofs.
+ * SECURITY: the seed is the only secret.  It must be unpredictable and FRESH for every proof -- a seed used twice, or one a verifier
+ * can guess, hides nothing.  seed = NULL draws it from the operating system (getrandom) and is the right choice outside tests.
+ * Hiding commitments are ONE ingredient of a zero-knowledge prover: the reference randomises neither the trace nor the quotient, Miden's
+ * own configurations use the non-hiding LMCS, and this library builds what the reference has and no more -- a proof made with salt on
+ * is NOT zero-knowledge.
+ * Not covered (MH_ERR_INVALID and a message while salt is on): mh_shard_*, mh_commit_traces_sharded, mh_prove_sharded and sharded
+ * sessions, mh_prove_miden*, mh_prove_precompile*, mh_check_* (the statement entries pin the reference's non-hiding configurations). */
+#define MH_MAX_SALT_ELEMS 8
+int mh_ctx_set_salt(mh_ctx* ctx, int salt_elems /* 0 = off (default) .. 8 */, const uint64_t seed[4] /* NULL: OS entropy (getrandom) */);
+int mh_ctx_get_salt(const mh_ctx* ctx);
 /* blake3(data) (host only; unit-parity entry point, like mh_poseidon2_permute) */
 void mh_blake3(const uint8_t* data, size_t n, uint8_t out32[32]);
 
@@ -141,7 +164,8 @@ int mh_tree_log_height(const mh_tree* t);
 /* LmcsTree::prove_batch (lmcs/lifted_tree.rs:155-180): for sorted, de-duplicated domain indices
  * (this call sorts/dedups), the opened rows of every matrix padded to `alignment`, then the
  * missing sibling digests bottom-up, left-to-right.  fields/commits must hold
- * n_idx * sum(aligned widths) and n_idx * depth * 4 felts at most. */
+ * n_idx * (sum(aligned widths) + mh_tree_salt_elems(t)) and n_idx * depth * 4 felts at most: a salted tree (mh_ctx_set_salt) hints
+ * each leaf's raw salt felts after its rows. */
 int mh_tree_open(mh_ctx* ctx, const mh_tree* t, const uint64_t* indices, size_t n_idx, size_t alignment,
                  uint64_t* fields, size_t* n_fields, uint64_t* commits, size_t* n_commit_felts);
 
@@ -150,6 +174,13 @@ int mh_tree_open(mh_ctx* ctx, const mh_tree* t, const uint64_t* indices, size_t 
 int mh_tree_download_lde(mh_ctx* ctx, const mh_tree* t, int mat, uint64_t* out_rowmajor_bitrev);
 /* Parity/debug: download all digest layers, leaf layer (domain order) first: (2H-1)*4 felts. */
 int mh_tree_download_layers(mh_ctx* ctx, const mh_tree* t, uint64_t* out);
+/* Hiding LMCS (mh_ctx_set_salt): the salt width the tree was committed with (0: not salted) and its number t in the salt PRF. */
+int mh_tree_salt_elems(const mh_tree* t);
+uint64_t mh_tree_salt_index(const mh_tree* t);
+/* Parity/debug: the tree's salt matrix, regenerated: [2^log_height][salt_elems], PHYSICAL (bit-reversed) row order like
+ * mh_tree_download_lde (lifted_tree.rs:300-306) -- the matrix that, appended to the tree's LDEs, gives its leaves.  It IS the secret
+ * the commitment hides behind.  MH_ERR_INVALID for an unsalted tree. */
+int mh_tree_download_salt(mh_ctx* ctx, const mh_tree* t, uint64_t* out);
 
 /* ---- coset-sharded commitment across the GPUs of a node (one process + one ctx per GPU) -------- */
 /* The LDE is stored coset-major, so rank k of `world` (a power of two <= 2^log_blowup) owns cosets
@@ -412,6 +443,14 @@ int mh_verify_lmcs(int lmcs, const mh_pcs_params* params, int n_airs, const uint
                    const uint64_t challenger_state[12], const uint64_t* pre_observe, size_t n_pre_observe, const uint64_t* fields,
                    size_t n_fields, const uint64_t* commitments, size_t n_commitments, const uint64_t* preprocessed_root,
                    mh_external_assertions external, void* external_user, uint64_t digest[4], char* err, size_t err_cap);
+/* mh_verify_lmcs for a proof made under a hiding LMCS (mh_ctx_set_salt, salt_elems = 0 .. MH_MAX_SALT_ELEMS): every opened leaf of every
+ * tree -- preprocessed, main, aux, quotient, each FRI round -- is read as `rows + salt` and the salt is absorbed last
+ * (lmcs/proof.rs:108-137).  preprocessed_root is the root of the SALTED setup tree.  salt_elems = 0 is mh_verify_lmcs. */
+int mh_verify_hiding(int lmcs, int salt_elems, const mh_pcs_params* params, int n_airs, const uint64_t* const* air_blobs,
+                     const size_t* air_blob_words, const uint8_t* log_trace_heights, const uint64_t* public_values, size_t n_public_values,
+                     const uint64_t challenger_state[12], const uint64_t* pre_observe, size_t n_pre_observe, const uint64_t* fields,
+                     size_t n_fields, const uint64_t* commitments, size_t n_commitments, const uint64_t* preprocessed_root,
+                     mh_external_assertions external, void* external_user, uint64_t digest[4], char* err, size_t err_cap);
 /* A ready-made mh_external_assertions: one assertion, the sum over the instances of their aux value 0 (the LogUp accumulator
  * final, `committed_finals` of air/src/lookup/aux_builder.rs) -- the balance of a bus statement with no boundary corrections. */
 int mh_external_logup_balance(void* user, const uint64_t* randomness, size_t n_randomness, const uint64_t* const* aux_values,

@@ -39,7 +39,10 @@ EXPORTS = [
     "mh_miden_challenger_state", "mh_miden_hash_kernel_digests", "mh_miden_pre_observe", "mh_miden_eval_external", "mh_miden_air_blob",
     "mh_check_constraints", "mh_check_miden", "mh_check_miden_traces", "mh_check_precompile", "mh_check_precompile_traces",
     "mh_check_balance", "mh_check_balance_miden", "mh_check_balance_miden_traces", "mh_check_balance_precompile", "mh_check_balance_precompile_traces",
+    "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
 ]
+
+MH_MAX_SALT_ELEMS = 8  # mh_ctx_set_salt: the largest salt width of the hiding LMCS
 
 # the in-tree cache of precompiled constraint kernels (filled by __graft_entry__.build() / tools/jit_precompile.py); $MH_JIT_CACHE_DIR wins
 # It is consulted READ-ONLY ($MH_JIT_CACHE_RO_DIR): kernels this box has to compile itself (another hiprtc version, another AIR) go to
@@ -197,6 +200,12 @@ def load_library():
     lib.mh_trace_free.argtypes = [C.c_void_p]
     lib.mh_tree_free.argtypes = [C.c_void_p]
     lib.mh_tree_log_height.argtypes = [C.c_void_p]
+    lib.mh_ctx_set_salt.argtypes = [C.c_void_p, C.c_int, u64p]
+    lib.mh_ctx_get_salt.argtypes = [C.c_void_p]
+    lib.mh_tree_salt_elems.argtypes = [C.c_void_p]
+    lib.mh_tree_salt_index.argtypes = [C.c_void_p]
+    lib.mh_tree_salt_index.restype = C.c_uint64
+    lib.mh_tree_download_salt.argtypes = [C.c_void_p, C.c_void_p, u64p]
     lib.mh_air_free.argtypes = [C.c_void_p]
     lib.mh_air_log_quotient_degree.argtypes = [C.c_void_p]
     lib.mh_proof_free.argtypes = [C.c_void_p]
@@ -320,6 +329,18 @@ class Ctx:
         self.check(self.lib.mh_ctx_set_lmcs(self.h, self.LMCS[name]))
         self.lmcs_id = self.LMCS[name]
 
+    def set_salt(self, n, seed=None):
+        """mh_ctx_set_salt: the hiding LMCS (lmcs/hiding_config.rs) with `n` salt felts per leaf (0 = off) for every tree committed from
+        now on.  seed = four integers (reduced mod p) -- secret and fresh per proof -- or None: drawn from the operating system.  Hiding
+        commitments alone do not make a proof zero-knowledge (include/midenhip.h)."""
+        key = _arr([int(x) % (1 << 64) for x in seed]) if seed is not None else None
+        if key is not None and key.size != 4:
+            raise MidenHipError("set_salt: the seed is four field elements")
+        self.check(self.lib.mh_ctx_set_salt(self.h, C.c_int(int(n)), _ptr(key) if key is not None else None))
+
+    def get_salt(self):
+        return int(self.lib.mh_ctx_get_salt(self.h))
+
     def upload_trace(self, matrix):
         return Trace(self, matrix)
 
@@ -428,6 +449,14 @@ class LmcsTree:
         ctx._children.add(self)
         self.widths, self.log_heights, self.log_blowup = widths, log_heights, log_blowup
         self.log_height = ctx.lib.mh_tree_log_height(h)
+        self.salt_elems = int(ctx.lib.mh_tree_salt_elems(h))   # hiding LMCS: salt felts per leaf (0: an ordinary tree)
+        self.salt_index = int(ctx.lib.mh_tree_salt_index(h))   # ... and the tree's number in the salt PRF
+
+    def salt(self):
+        """mh_tree_download_salt: the tree's salt matrix [2^log_height, salt_elems], physical (bit-reversed) row order like download_lde."""
+        out = np.zeros((1 << self.log_height, self.salt_elems), dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.mh_tree_download_salt(self.ctx.h, self.h, _ptr(out)))
+        return out
 
     def root(self):
         r = np.zeros(4, dtype=np.uint64)
@@ -438,7 +467,7 @@ class LmcsTree:
         """-> (hinted felts, hinted commitments[k][4]) exactly as streamed into the transcript."""
         idx = _arr(list(indices))
         n = idx.size
-        tot_w = sum(((w + alignment - 1) // alignment) * alignment for w in self.widths)
+        tot_w = sum(((w + alignment - 1) // alignment) * alignment for w in self.widths) + self.salt_elems  # rows + raw salt
         fields = np.zeros(max(1, n * tot_w), dtype=np.uint64)
         commits = np.zeros(max(1, n * self.log_height * 4), dtype=np.uint64)
         nf, nc = C.c_size_t(0), C.c_size_t(0)
@@ -841,11 +870,12 @@ def external_callback(fn):
 
 
 def verify(airs, log_trace_heights, public_values, params, challenger_state, pre_observe, fields, commitments,
-           preprocessed_root=None, external=None, lmcs="poseidon2"):
+           preprocessed_root=None, external=None, lmcs="poseidon2", salt_elems=0):
     """mh_verify / mh_verify_ex (host only, no GPU): airs = dag.Air objects in instance order; preprocessed_root = the setup
     commitment when some AIR has preprocessed columns (it must also be in pre_observe); external = the statement's cross-AIR
     assertions: an EXTERNAL_FN / external_callback(...) object, the string "logup_balance" for the library's
-    mh_external_logup_balance, or "precompile_session" / "precompile_session_ec_only" for its mh_external_precompile_session.  Returns (ok, digest or message)."""
+    mh_external_logup_balance, or "precompile_session" / "precompile_session_ec_only" for its mh_external_precompile_session.
+    salt_elems > 0: mh_verify_hiding, for a proof made after Ctx.set_salt(salt_elems).  Returns (ok, digest or message)."""
     lib = load_library()
     n = len(airs)
     blobs = [_arr(a.blob) for a in airs]
@@ -862,7 +892,13 @@ def verify(airs, log_trace_heights, public_values, params, challenger_state, pre
     ext_user = None
     if external in ("precompile_session", "precompile_session_ec_only"):   # the library's ChipletMultiAir::eval_external (session/prove.rs:243-256)
         external = C.cast(lib.mh_external_precompile_session_ec_only if external.endswith("ec_only") else lib.mh_external_precompile_session, EXTERNAL_FN)
-    if lmcs != "poseidon2":  # mh_verify_lmcs: the other algebraic configurations ("rpo", "rpx")
+    if salt_elems:  # mh_verify_hiding: any configuration, `rows + salt` per opened leaf
+        ext = C.cast(lib.mh_external_logup_balance, EXTERNAL_FN) if external == "logup_balance" else external
+        rc = lib.mh_verify_hiding(C.c_int(Ctx.LMCS[lmcs]), C.c_int(int(salt_elems)), C.byref(p), C.c_int(n), bp, bl, lh, _ptr(pub),
+                                  C.c_size_t(len(public_values)), _ptr(st), _ptr(pre), C.c_size_t(len(pre_observe)), _ptr(f),
+                                  C.c_size_t(f.size), _ptr(c), C.c_size_t(c.size // 4), _ptr(proot) if proot is not None else None,
+                                  ext if ext is not None else C.cast(None, EXTERNAL_FN), ext_user, _ptr(digest), err, C.c_size_t(512))
+    elif lmcs != "poseidon2":  # mh_verify_lmcs: the other algebraic configurations ("rpo", "rpx")
         ext = C.cast(lib.mh_external_logup_balance, EXTERNAL_FN) if external == "logup_balance" else external
         rc = lib.mh_verify_lmcs(C.c_int(Ctx.LMCS[lmcs]), C.byref(p), C.c_int(n), bp, bl, lh, _ptr(pub), C.c_size_t(len(public_values)),
                                 _ptr(st), _ptr(pre), C.c_size_t(len(pre_observe)), _ptr(f), C.c_size_t(f.size), _ptr(c),

@@ -471,6 +471,7 @@ int balance_statement(mh_ctx* c, int n_airs, mh_air* const* airs, mh_trace* cons
     MH_REQUIRE(n_entries && n_pushes && (entries || !entry_cap) && (pushes || !push_cap), "null argument");
     MH_REQUIRE((flags & ~MH_CHECK_EXACT) == 0, "unknown check flags");
     *n_entries = *n_pushes = 0;
+    MH_REQUIRE_NO_SALT(c, "mh_check_balance*");
     HIP_CHECK(hipSetDevice(c->device));
     size_t max_rand = 0;
     std::vector<BalanceInput> in;
@@ -515,6 +516,7 @@ extern "C" int mh_check_balance(mh_ctx* c, int n, const mh_lookup* const* lookup
     MH_REQUIRE((randomness || !n_randomness) && ((boundary_denoms && boundary_signs) || !n_boundary), "null value array");
     MH_REQUIRE((flags & ~MH_CHECK_EXACT) == 0, "unknown check flags");
     *n_entries = *n_pushes = 0;
+    MH_REQUIRE_NO_SALT(c, "mh_check_balance*");
     HIP_CHECK(hipSetDevice(c->device));
     std::vector<BalanceInput> in;
     for (int i = 0; i < n; i++) in.push_back(BalanceInput{lookups[i], traces[i], preprocessed ? preprocessed[i] : nullptr});

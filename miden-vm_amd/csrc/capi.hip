@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <sys/random.h>
 
 #define MH_TRY(ctx_expr) mh_ctx* _c = (ctx_expr); PoolScope _ps(_c); try {
 #define MH_CATCH                                                   \
@@ -50,6 +51,38 @@ int mh_ctx_set_lmcs(mh_ctx* c, int lmcs) {
   return 0;
 }
 int mh_ctx_get_lmcs(const mh_ctx* c) { return c ? c->lmcs : -1; }
+
+// Hiding LMCS: salt_elems felts per leaf of every tree committed from now on, derived from `seed` (salt.cuh).  Restarts the tree count.
+int mh_ctx_set_salt(mh_ctx* c, int salt_elems, const uint64_t seed[4]) {
+  if (!c) return MH_ERR_INVALID;
+  if (salt_elems < 0 || salt_elems > MH_MAX_SALT_ELEMS) {
+    c->err = "salt_elems must be in 0..MH_MAX_SALT_ELEMS";
+    return MH_ERR_INVALID;
+  }
+  SaltArgs sa;
+  sa.n = salt_elems;
+  if (salt_elems) {
+    uint64_t drawn[4];
+    if (!seed) {  // the operating system's entropy: a secret, fresh seed per call
+      size_t got = 0;
+      while (got < sizeof drawn) {
+        const ssize_t k = getrandom(reinterpret_cast<uint8_t*>(drawn) + got, sizeof drawn - got, 0);
+        if (k <= 0) {
+          c->err = "mh_ctx_set_salt: getrandom failed";
+          return MH_ERR_INTERNAL;
+        }
+        got += (size_t)k;
+      }
+      seed = drawn;
+    }
+    for (int i = 0; i < 4; i++) sa.key[i] = gl_canon(seed[i]);
+  }
+  c->salt = sa;
+  return MH_OK;
+}
+int mh_ctx_get_salt(const mh_ctx* c) { return c ? c->salt.n : -1; }
+int mh_tree_salt_elems(const mh_tree* t) { return t ? t->salt.n : -1; }
+uint64_t mh_tree_salt_index(const mh_tree* t) { return t ? t->salt.tree : 0; }
 void mh_blake3(const uint8_t* data, size_t n, uint8_t out32[32]) { b3::hash_bytes(data, n, out32); }
 
 int mh_ctx_create(int device_id, mh_ctx** out) {
@@ -338,6 +371,7 @@ int mh_tree_open(mh_ctx* c, const mh_tree* t, const uint64_t* indices, size_t n_
   std::vector<size_t> idx(indices, indices + n_idx);
   std::sort(idx.begin(), idx.end());
   idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
+  MH_REQUIRE(!t->salt.n || t->ctx == c, "a salted tree is opened on the context that committed it");
   std::vector<u64> f, cm;
   lmcs_open(c, t, idx, alignment, f, cm);
   if (!f.empty()) memcpy(fields, f.data(), f.size() * 8);
@@ -357,6 +391,21 @@ int mh_tree_download_lde(mh_ctx* c, const mh_tree* t, int mat, uint64_t* out) {
   MH_LAUNCH(k_lde_to_reference_layout, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, m.lde.u(),
                      tmp.u(), m.log_n, t->log_blowup, m.width);
   HIP_CHECK(hipMemcpyAsync(out, tmp.p, total * 8, hipMemcpyDeviceToHost, c->stream));
+  c->sync();
+  MH_CATCH
+}
+
+int mh_tree_download_salt(mh_ctx* c, const mh_tree* t, uint64_t* out) {
+  MH_TRY(c)
+  MH_REQUIRE(c && t && out, "bad argument");
+  MH_REQUIRE(t->ctx == c, "tree of another context");
+  MH_REQUIRE(t->salt.n > 0, "the tree is not salted (mh_ctx_set_salt was off when it was committed)");
+  MH_REQUIRE(t->shard_logG == 0, "internal: a salted tree cannot be sharded");
+  HIP_CHECK(hipSetDevice(c->device));
+  const size_t rows = (size_t)1 << t->log_height;
+  DevBuf tmp(rows * (size_t)t->salt.n * 8);
+  lmcs_salt_rows(c, t->salt, nullptr, rows, tmp.u());
+  HIP_CHECK(hipMemcpyAsync(out, tmp.p, tmp.bytes, hipMemcpyDeviceToHost, c->stream));
   c->sync();
   MH_CATCH
 }

@@ -396,6 +396,7 @@ int check_statement(mh_ctx* c, int n_airs, mh_air* const* airs, mh_trace* const*
     MH_REQUIRE(n_entries && (out || !cap), "null n_entries / out");
     MH_REQUIRE((flags & ~MH_CHECK_EXACT) == 0, "unknown check flags");
     *n_entries = 0;
+    MH_REQUIRE_NO_SALT(c, "mh_check_*");
     HIP_CHECK(hipSetDevice(c->device));
     size_t max_rand = 0;
     for (int i = 0; i < n_airs; i++) {
@@ -467,6 +468,7 @@ extern "C" int mh_check_constraints(mh_ctx* c, const mh_air* air, const mh_trace
   try {
     MH_REQUIRE(air && main_trace && n_entries && (out || !cap), "null argument");
     MH_REQUIRE(air->ctx == c && main_trace->ctx == c && (!aux || aux->ctx == c), "AIR / trace of another context");
+    MH_REQUIRE_NO_SALT(c, "mh_check_constraints");
     MH_REQUIRE((public_values || !n_public) && (randomness || !n_randomness) && (aux_values || !n_aux_values), "null value array");
     MH_REQUIRE((flags & ~MH_CHECK_EXACT) == 0, "unknown check flags");
     *n_entries = 0;

@@ -125,6 +125,14 @@ struct DevBuf {
   u64* u() const { return (u64*)p; }
 };
 
+// Hiding LMCS (mh_ctx_set_salt; the reference's HidingLmcsConfig, lmcs/hiding_config.rs): `n` salt felts per leaf (0 = off), derived
+// from `key` by a Poseidon2 PRF (salt.cuh), never stored.  `tree` = the tree's number among the salted trees of its context.
+struct SaltArgs {
+  u64 key[4] = {0, 0, 0, 0};
+  u64 tree = 0;
+  int n = 0;
+};
+
 struct ProfEntry {
   double ms = 0;
   double bytes = 0;  // algorithmic bytes attributed by the caller
@@ -152,6 +160,7 @@ struct mh_ctx {
   std::map<std::string, DevBuf> tables;
   std::map<std::string, std::vector<size_t>> table_index;  // host-side offsets into `tables` entries
   int lmcs = 0;  // MH_LMCS_POSEIDON2 / MH_LMCS_BLAKE3: the commitment scheme's hasher (StarkConfig::Lmcs), mh_ctx_set_lmcs
+  SaltArgs salt;      // mh_ctx_set_salt: salt.n felts per leaf of every tree committed from now on; salt.tree = the next tree's number
   bool ntt_big_lds_attr = false;  // hipFuncSetAttribute(MaxDynamicSharedMemorySize) done for this ctx's device
 
   hipEvent_t get_event();
@@ -178,6 +187,11 @@ struct mh_ctx {
   void host_give(void* p, size_t bytes) { host_pool.emplace_back(p, bytes); }
   const u64* twiddles(int log_n, bool inverse);
 };
+
+// Entries the hiding LMCS does not cover (sharded commitments, the statement provers, the checkers): a code and a message, never a
+// proof whose trees are salted only in part.
+#define MH_REQUIRE_NO_SALT(c, entry) \
+  MH_REQUIRE(!(c) || !(c)->salt.n, std::string(entry) + " is not available while the context's hiding LMCS is on (mh_ctx_set_salt)")
 
 // RAII: make `c`'s allocation pool current for the duration of one C-ABI call.
 struct PoolScope {

@@ -20,6 +20,7 @@
 #include "poseidon2_fast.cuh"
 #define RESCUE_FAST 1  // S-boxes through p2f_mulN (poseidon2_fast.cuh is included above)
 #include "rescue.cuh"
+#include "salt.cuh"
 
 __device__ __forceinline__ e2 ld_e2(const u64* p, size_t idx) {
   const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(p + 2 * idx);
@@ -32,8 +33,11 @@ __device__ __forceinline__ u32 fri_row_pos(u32 p, int log_arity) { return bitrev
 
 // ---- leaf digests: one permutation per leaf for arity 4 (8 felts = the rate), ---------------------
 // sponge over 2*arity felts in general.
-__global__ __launch_bounds__(256) void k_fri_leaf_hash(const u64* __restrict__ ev, int log_rows /* Nl */, int cbits, int log_arity,
-                                                       u64* __restrict__ digests) {
+// Hiding LMCS (salt.cuh): as in lmcs.hip every leaf kernel's body is a template; the salt-off instantiation keeps its name, arguments
+// and code, the salted kernel absorbs the leaf's salt row behind the arity-coset as one more matrix.
+template <bool SALT>
+__device__ __forceinline__ void fri_leaf_hash_body(const u64* __restrict__ ev, int log_rows /* Nl */, int cbits, int log_arity,
+                                                   u64* __restrict__ digests, const SaltArgs* sa) {
   const int log_q = log_rows - log_arity;  // rows per coset after grouping
   const size_t leaves = (size_t)1 << (log_q + cbits);
   const size_t s = blockIdx.x * (size_t)256 + threadIdx.x;
@@ -54,14 +58,24 @@ __global__ __launch_bounds__(256) void k_fri_leaf_hash(const u64* __restrict__ e
     }
     p2f_permute(st);
   }
+  if constexpr (SALT) salt_absorb_p2(st, *sa, salt_phys_row(j, r0, cbits, log_q + cbits));
   ulonglong2* o = reinterpret_cast<ulonglong2*>(digests + 4 * s);
   o[0] = make_ulonglong2(st[0], st[1]);
   o[1] = make_ulonglong2(st[2], st[3]);
 }
+__global__ __launch_bounds__(256) void k_fri_leaf_hash(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
+                                                       u64* __restrict__ digests) {
+  fri_leaf_hash_body<false>(ev, log_rows, cbits, log_arity, digests, nullptr);
+}
+__global__ __launch_bounds__(256) void k_fri_leaf_hash_salted(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
+                                                              u64* __restrict__ digests, SaltArgs sa) {
+  fri_leaf_hash_body<true>(ev, log_rows, cbits, log_arity, digests, &sa);
+}
 
 // Blake3 LMCS (air/src/config.rs:275-289): leaf = blake3(32 zero bytes || the row's 2 * arity felts, 8 LE bytes each)
-__global__ __launch_bounds__(256) void k_fri_leaf_hash_b3(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
-                                                          u64* __restrict__ digests) {
+template <bool SALT>
+__device__ __forceinline__ void fri_leaf_hash_b3_body(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
+                                                      u64* __restrict__ digests, const SaltArgs* sa) {
   const int log_q = log_rows - log_arity;
   const size_t leaves = (size_t)1 << (log_q + cbits);
   const size_t s = blockIdx.x * (size_t)256 + threadIdx.x;
@@ -87,13 +101,23 @@ __global__ __launch_bounds__(256) void k_fri_leaf_hash_b3(const u64* __restrict_
     if (b + 1 < n_blocks) h.block(m);
     else h.finish(m, total - 64 * b, out);
   }
+  if constexpr (SALT) salt_absorb_b3(out, *sa, salt_phys_row(j, r0, cbits, log_q + cbits));
 #pragma unroll
   for (int i = 0; i < 4; i++) digests[4 * s + i] = (u64)out[2 * i] | ((u64)out[2 * i + 1] << 32);
 }
+__global__ __launch_bounds__(256) void k_fri_leaf_hash_b3(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
+                                                          u64* __restrict__ digests) {
+  fri_leaf_hash_b3_body<false>(ev, log_rows, cbits, log_arity, digests, nullptr);
+}
+__global__ __launch_bounds__(256) void k_fri_leaf_hash_b3_salted(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
+                                                                 u64* __restrict__ digests, SaltArgs sa) {
+  fri_leaf_hash_b3_body<true>(ev, log_rows, cbits, log_arity, digests, &sa);
+}
 
 // RPO / RPX: k_fri_leaf_hash with the Rescue permutations
-__global__ __launch_bounds__(256) void k_fri_leaf_hash_alg(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
-                                                           u64* __restrict__ digests, int lmcs) {
+template <bool SALT>
+__device__ __forceinline__ void fri_leaf_hash_alg_body(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
+                                                       u64* __restrict__ digests, int lmcs, const SaltArgs* sa) {
   const int log_q = log_rows - log_arity;
   const size_t leaves = (size_t)1 << (log_q + cbits);
   const size_t s = blockIdx.x * (size_t)256 + threadIdx.x;
@@ -114,13 +138,23 @@ __global__ __launch_bounds__(256) void k_fri_leaf_hash_alg(const u64* __restrict
     }
     alg_permute(lmcs, st);
   }
+  if constexpr (SALT) salt_absorb_alg(st, *sa, salt_phys_row(j, r0, cbits, log_q + cbits), lmcs);
 #pragma unroll
   for (int i = 0; i < 4; i++) digests[4 * s + i] = st[i];
 }
+__global__ __launch_bounds__(256) void k_fri_leaf_hash_alg(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
+                                                           u64* __restrict__ digests, int lmcs) {
+  fri_leaf_hash_alg_body<false>(ev, log_rows, cbits, log_arity, digests, lmcs, nullptr);
+}
+__global__ __launch_bounds__(256) void k_fri_leaf_hash_alg_salted(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
+                                                                  u64* __restrict__ digests, int lmcs, SaltArgs sa) {
+  fri_leaf_hash_alg_body<true>(ev, log_rows, cbits, log_arity, digests, lmcs, &sa);
+}
 
 // Keccak LMCS: the sponge over the row's 2 * arity <= 16 felts = one permutation of (felts, zeros)
-__global__ __launch_bounds__(256) void k_fri_leaf_hash_kk(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
-                                                          u64* __restrict__ digests) {
+template <bool SALT>
+__device__ __forceinline__ void fri_leaf_hash_kk_body(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
+                                                      u64* __restrict__ digests, const SaltArgs* sa) {
   const int log_q = log_rows - log_arity;
   const size_t leaves = (size_t)1 << (log_q + cbits);
   const size_t s = blockIdx.x * (size_t)256 + threadIdx.x;
@@ -139,8 +173,17 @@ __global__ __launch_bounds__(256) void k_fri_leaf_hash_kk(const u64* __restrict_
     }
   }
   kk::f1600(st);
+  if constexpr (SALT) salt_absorb_kk(st, *sa, salt_phys_row(j, r0, cbits, log_q + cbits));
 #pragma unroll
   for (int i = 0; i < 4; i++) digests[4 * s + i] = st[i];
+}
+__global__ __launch_bounds__(256) void k_fri_leaf_hash_kk(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
+                                                          u64* __restrict__ digests) {
+  fri_leaf_hash_kk_body<false>(ev, log_rows, cbits, log_arity, digests, nullptr);
+}
+__global__ __launch_bounds__(256) void k_fri_leaf_hash_kk_salted(const u64* __restrict__ ev, int log_rows, int cbits, int log_arity,
+                                                                 u64* __restrict__ digests, SaltArgs sa) {
+  fri_leaf_hash_kk_body<true>(ev, log_rows, cbits, log_arity, digests, &sa);
 }
 
 // ---- fold ----------------------------------------------------------------------------------------
@@ -226,9 +269,21 @@ __global__ void k_fri_to_natural(const u64* ev, u64* out, int log_rows, int cbit
   st_e2(out, i, ld_e2(ev, (j << log_rows) + r));
 }
 
-void fri_leaf_hash(mh_ctx* c, const u64* ev, int log_rows, int cbits, int log_arity, u64* digests) {
+void fri_leaf_hash(mh_ctx* c, const u64* ev, int log_rows, int cbits, int log_arity, u64* digests, const SaltArgs* salt) {
   const size_t leaves = (size_t)1 << (log_rows - log_arity + cbits);
   ProfScope ps(c, "fri_leaf_hash", (double)leaves * (16.0 * (1 << log_arity) + 32.0));
+  if (salt) {
+    const dim3 grid((unsigned)((leaves + 255) / 256));
+    if (c->lmcs == MH_LMCS_RPO || c->lmcs == MH_LMCS_RPX)
+      MH_LAUNCH(k_fri_leaf_hash_alg_salted, grid, dim3(256), 0, c->stream, ev, log_rows, cbits, log_arity, digests, c->lmcs, *salt);
+    else if (c->lmcs == MH_LMCS_KECCAK)
+      MH_LAUNCH(k_fri_leaf_hash_kk_salted, grid, dim3(256), 0, c->stream, ev, log_rows, cbits, log_arity, digests, *salt);
+    else if (c->lmcs == MH_LMCS_BLAKE3)
+      MH_LAUNCH(k_fri_leaf_hash_b3_salted, grid, dim3(256), 0, c->stream, ev, log_rows, cbits, log_arity, digests, *salt);
+    else
+      MH_LAUNCH(k_fri_leaf_hash_salted, grid, dim3(256), 0, c->stream, ev, log_rows, cbits, log_arity, digests, *salt);
+    return;
+  }
   if (c->lmcs == MH_LMCS_RPO || c->lmcs == MH_LMCS_RPX)
     MH_LAUNCH(k_fri_leaf_hash_alg, dim3((unsigned)((leaves + 255) / 256)), dim3(256), 0, c->stream, ev, log_rows, cbits, log_arity, digests,
                        c->lmcs);

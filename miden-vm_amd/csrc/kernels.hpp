@@ -74,6 +74,7 @@ struct mh_tree {
   int log_blowup;  // number of coset bits in the leaf layer layout (may be 0)
   int log_height;  // tree depth L (leaves = 2^L)
   int lmcs = 0;    // MH_LMCS_* hasher the layers were built with (the context's, at build time)
+  SaltArgs salt;   // hiding LMCS: the PRF inputs of this tree's salt rows (salt.n = 0: an ordinary tree); set by lmcs_salt_assign
   std::vector<LdeMatrix> mats;
   // FRI round trees (fri.hip) commit one EF layer instead of LDE matrices: rows are rebuilt from it
   DevBuf fri_layer;      // EF pairs, coset-major [2^fri_log_cosets][2^fri_log_rows] (this rank's cosets)
@@ -103,9 +104,16 @@ double poseidon2_register_rate(mh_ctx* c);  // permutations/s with the state hel
 // Build leaf digests + all layers for `t->mats` (already filled); sets t->root.
 void lmcs_build_tree(mh_ctx* c, mh_tree* t);
 // Pieces of the above for trees whose leaf digests come from another kernel (FRI rounds):
-void lmcs_hash_leaves(mh_ctx* c, const std::vector<LdeMatrix>& mats, int lb, u64* digests);
+// salt (hiding LMCS, null = none): absorbed after the last matrix as one more matrix of the tallest height (lifted_tree.rs:233-245)
+void lmcs_hash_leaves(mh_ctx* c, const std::vector<LdeMatrix>& mats, int lb, u64* digests, const SaltArgs* salt = nullptr);
 // the leaves [q_begin, q_begin + q_count) only (a group of cosets of a tree whose matrices all have one height)
-void lmcs_hash_leaves_range(mh_ctx* c, const std::vector<LdeMatrix>& mats, int lb, u64* digests, size_t q_begin, size_t q_count);
+void lmcs_hash_leaves_range(mh_ctx* c, const std::vector<LdeMatrix>& mats, int lb, u64* digests, size_t q_begin, size_t q_count,
+                            const SaltArgs* salt = nullptr);
+// Hiding LMCS: give `t` the context's salt setting and the next tree number (no-op with salt off).  Call it once, before the leaves.
+void lmcs_salt_assign(mh_ctx* c, mh_tree* t);
+const SaltArgs* lmcs_salt_of(const mh_tree* t);  // &t->salt, or null for an unsalted tree
+// out[k][salt.n] = the salt row of physical (bit-reversed) leaf row rows[k]; rows = null: rows 0 .. n_rows - 1 (device pointers)
+void lmcs_salt_rows(mh_ctx* c, const SaltArgs& salt, const u64* rows, size_t n_rows, u64* out);
 bool lmcs_leaves_rangeable(mh_ctx* c, const std::vector<LdeMatrix>& mats);
 void lmcs_alloc_layers(mh_tree* t, int log_height);  // sets log_height, layer_off, nodes
 u64* lmcs_leaf_layer(mh_tree* t);                     // device pointer of the leaf digest layer
@@ -117,7 +125,9 @@ void lmcs_open(mh_ctx* c, const mh_tree* t, const std::vector<size_t>& sorted_un
 struct OpenPlan {
   size_t first = 0, n_fields = 0, n = 0;                     // this tree's slice of the gather list: rows, then sibling digests
   std::vector<std::pair<size_t, const u64*>> cap_fill;       // (offset in the slice, host digest of the sharded tree's cap)
+  DevBuf salt_rows;                                          // hiding LMCS: the opened leaves' salt rows, regenerated; the gather reads them
 };
+// (enqueues the salt-row kernel of a salted tree on the tree's context: the plan must outlive the gather)
 OpenPlan lmcs_open_plan(const mh_tree* t, const std::vector<size_t>& idx, size_t alignment, const Dist* dist, std::vector<const u64*>& ptrs);
 void lmcs_open_run(mh_ctx* c, const std::vector<const u64*>& ptrs, const Dist* dist, std::vector<u64>& host);
 void lmcs_open_take(const OpenPlan& plan, std::vector<u64>& host, std::vector<u64>& fields, std::vector<u64>& commitments);
@@ -165,7 +175,7 @@ void deep_ood_eval_matrix(mh_ctx* c, const LdeMatrix& m, int log_blowup, e2 y0, 
 void deep_assemble(mh_ctx* c, const std::vector<const LdeMatrix*>& mats, const std::vector<uint32_t>& coef_off, int log_n, int log_blowup,
                    const std::vector<e2>& negc, e2 z0, e2 z1, e2 fred0, e2 fred1, e2 beta, u64* out);
 // ---- fri.hip -----------------------------------------------------------------------------------
-void fri_leaf_hash(mh_ctx* c, const u64* ev, int log_rows, int cbits, int log_arity, u64* digests);
+void fri_leaf_hash(mh_ctx* c, const u64* ev, int log_rows, int cbits, int log_arity, u64* digests, const SaltArgs* salt = nullptr);
 // cbits = coset bits stored locally, cbits_global / coset0 locate them in the whole layer
 void fri_fold(mh_ctx* c, const u64* ev, int log_rows, int cbits, int cbits_global, size_t coset0, int log_arity, e2 beta, u64* out);
 void fri_to_natural(mh_ctx* c, const u64* ev, int log_rows, int cbits, u64* out);

@@ -27,6 +27,7 @@
 #define RESCUE_FAST 1  // S-boxes through p2f_mulN (poseidon2_fast.cuh is included above)
 #include "rescue.cuh"
 #include "gl.cuh"
+#include "salt.cuh"
 #include <algorithm>
 #include <cstring>
 
@@ -97,7 +98,11 @@ struct LeafArgs {
   size_t q_begin, q_count;  // the leaves this launch hashes; q_count = 0: all of them
 };
 
-__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb(LeafArgs a) {
+// The salted forms (hiding LMCS, salt.cuh) are kernels of their own: each leaf kernel's body is a template, the salt-off instantiation
+// keeps its name, its arguments and its code, and the salted one derives the leaf's salt row after the last matrix and absorbs it as
+// one more matrix.  Only the launch of a tree's LAST height group is salted; earlier groups carry state as ever.
+template <bool SALT>
+__device__ __forceinline__ void leaf_absorb_body(const LeafArgs& a, const SaltArgs* sa) {
   const size_t leaves = (size_t)1 << (a.log_n + a.log_blowup);
   const size_t q = a.q_begin + blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (q >= (a.q_count ? a.q_begin + a.q_count : leaves)) return;
@@ -124,6 +129,7 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb(LeafArgs a) {
       p2f_permute(s);
     }
   }
+  if constexpr (SALT) salt_absorb_p2(s, *sa, salt_phys_row(j, r, a.log_blowup, a.log_n + a.log_blowup));
   if (a.digest_out) {
     ulonglong2* o = reinterpret_cast<ulonglong2*>(a.digest_out + 4 * q);
     o[0] = make_ulonglong2(s[0], s[1]);
@@ -133,12 +139,15 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb(LeafArgs a) {
     for (int i = 0; i < 12; i++) a.state_out[i * leaves + q] = s[i];
   }
 }
+__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb(LeafArgs a) { leaf_absorb_body<false>(a, nullptr); }
+__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_salted(LeafArgs a, SaltArgs sa) { leaf_absorb_body<true>(a, &sa); }
 
 // ---- Blake3 LMCS (mh_ctx_set_lmcs(MH_LMCS_BLAKE3)): same launch structure, the state is the 32-byte digest itself ----
 // One thread per leaf; per matrix one hash of  state || row  (chaining.rs:32-50).  Block 0 = the state and the first four
 // felts, every later block eight felts (coalesced column reads, as in k_leaf_absorb); state_in / state_out / digest_out
 // are all [leaves][4] u64 (a digest = its 32 bytes little-endian).
-__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_b3(LeafArgs a) {
+template <bool SALT>
+__device__ __forceinline__ void leaf_absorb_b3_body(const LeafArgs& a, const SaltArgs* sa) {
   const size_t leaves = (size_t)1 << (a.log_n + a.log_blowup);
   const size_t q = a.q_begin + blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (q >= (a.q_count ? a.q_begin + a.q_count : leaves)) return;
@@ -186,10 +195,13 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_b3(LeafArgs a) {
       else h.finish(m, total - 64 * b, st);
     }
   }
+  if constexpr (SALT) salt_absorb_b3(st, *sa, salt_phys_row(j, r, a.log_blowup, a.log_n + a.log_blowup));
   u64* o = (a.digest_out ? a.digest_out : a.state_out) + 4 * q;
 #pragma unroll
   for (int i = 0; i < 4; i++) o[i] = (u64)st[2 * i] | ((u64)st[2 * i + 1] << 32);
 }
+__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_b3(LeafArgs a) { leaf_absorb_b3_body<false>(a, nullptr); }
+__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_b3_salted(LeafArgs a, SaltArgs sa) { leaf_absorb_b3_body<true>(a, &sa); }
 __global__ __launch_bounds__(256) void k_compress_b3(const u64* __restrict__ in, u64* __restrict__ out, size_t n_out, int log_n_coset) {
   const size_t q = blockIdx.x * (size_t)256 + threadIdx.x;
   if (q >= n_out) return;
@@ -244,7 +256,8 @@ __global__ __launch_bounds__(256) void k_compress_b3_top(u64* nodes, int log_hei
 
 // ---- RPO / RPX (MH_LMCS_RPO, MH_LMCS_RPX): the sponge and the compression of the Poseidon2 LMCS with the Rescue permutations
 // (rescue.cuh; plain arithmetic, one state per lane -- supported, not tuned) ----
-__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_alg(LeafArgs a, int lmcs) {
+template <bool SALT>
+__device__ __forceinline__ void leaf_absorb_alg_body(const LeafArgs& a, int lmcs, const SaltArgs* sa) {
   const size_t leaves = (size_t)1 << (a.log_n + a.log_blowup);
   const size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (q >= leaves) return;
@@ -271,6 +284,7 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_alg(LeafArgs a, in
       alg_permute(lmcs, s);
     }
   }
+  if constexpr (SALT) salt_absorb_alg(s, *sa, salt_phys_row(j, r, a.log_blowup, a.log_n + a.log_blowup), lmcs);
   if (a.digest_out) {
 #pragma unroll
     for (int i = 0; i < 4; i++) a.digest_out[4 * q + i] = s[i];
@@ -278,6 +292,10 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_alg(LeafArgs a, in
 #pragma unroll
     for (int i = 0; i < 12; i++) a.state_out[i * leaves + q] = s[i];
   }
+}
+__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_alg(LeafArgs a, int lmcs) { leaf_absorb_alg_body<false>(a, lmcs, nullptr); }
+__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_alg_salted(LeafArgs a, int lmcs, SaltArgs sa) {
+  leaf_absorb_alg_body<true>(a, lmcs, &sa);
 }
 __global__ __launch_bounds__(256) void k_compress_alg(const u64* __restrict__ in, u64* __restrict__ out, size_t n_out, int log_n_coset,
                                                       int lmcs) {
@@ -306,7 +324,8 @@ __global__ __launch_bounds__(256) void k_compress_alg(const u64* __restrict__ in
 }
 
 // ---- Keccak LMCS (MH_LMCS_KECCAK): the sponge of k_leaf_absorb with Keccak-f[1600], 25 lanes, rate 17 ----
-__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_kk(LeafArgs a) {
+template <bool SALT>
+__device__ __forceinline__ void leaf_absorb_kk_body(const LeafArgs& a, const SaltArgs* sa) {
   const size_t leaves = (size_t)1 << (a.log_n + a.log_blowup);
   const size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (q >= leaves) return;
@@ -333,6 +352,7 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_kk(LeafArgs a) {
       kk::f1600(s);
     }
   }
+  if constexpr (SALT) salt_absorb_kk(s, *sa, salt_phys_row(j, r, a.log_blowup, a.log_n + a.log_blowup));
   if (a.digest_out) {
 #pragma unroll
     for (int i = 0; i < 4; i++) a.digest_out[4 * q + i] = s[i];
@@ -341,6 +361,30 @@ __global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_kk(LeafArgs a) {
     for (int i = 0; i < 25; i++) a.state_out[i * leaves + q] = s[i];
   }
 }
+__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_kk(LeafArgs a) { leaf_absorb_kk_body<false>(a, nullptr); }
+__global__ __launch_bounds__(LEAF_THREADS) void k_leaf_absorb_kk_salted(LeafArgs a, SaltArgs sa) { leaf_absorb_kk_body<true>(a, &sa); }
+
+// out[k][0 .. n) = the salt row of physical leaf row rows[k] (rows = null: row k): what an opening hints after the leaf's rows and
+// what mh_tree_download_salt returns.  The leaf kernels above never read it.
+__global__ __launch_bounds__(256) void k_salt_rows(SaltArgs sa, const u64* __restrict__ rows, size_t n_rows, u64* __restrict__ out) {
+  const size_t k = blockIdx.x * (size_t)256 + threadIdx.x;
+  if (k >= n_rows) return;
+  u64 z[12];
+  salt_row(sa, rows ? rows[k] : (u64)k, z);
+#pragma unroll
+  for (int e = 0; e < 8; e++)
+    if (e < sa.n) out[k * (size_t)sa.n + e] = z[e];
+}
+void lmcs_salt_rows(mh_ctx* c, const SaltArgs& salt, const u64* rows, size_t n_rows, u64* out) {
+  if (!n_rows || !salt.n) return;
+  MH_LAUNCH(k_salt_rows, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, c->stream, salt, rows, n_rows, out);
+}
+void lmcs_salt_assign(mh_ctx* c, mh_tree* t) {
+  if (!c->salt.n) return;
+  t->salt = c->salt;
+  c->salt.tree++;
+}
+const SaltArgs* lmcs_salt_of(const mh_tree* t) { return t->salt.n ? &t->salt : nullptr; }
 __global__ __launch_bounds__(256) void k_compress_kk(const u64* __restrict__ in, u64* __restrict__ out, size_t n_out, int log_n_coset) {
   const size_t q = blockIdx.x * (size_t)256 + threadIdx.x;
   if (q >= n_out) return;
@@ -548,7 +592,7 @@ void lmcs_compress_layers(mh_ctx* c, mh_tree* t) {
 void lmcs_build_tree(mh_ctx* c, mh_tree* t) {
   MH_REQUIRE(!t->mats.empty(), "cannot commit empty batch");
   lmcs_alloc_layers(t, t->mats.back().log_n + t->log_blowup);
-  lmcs_hash_leaves(c, t->mats, t->log_blowup, lmcs_leaf_layer(t));
+  lmcs_hash_leaves(c, t->mats, t->log_blowup, lmcs_leaf_layer(t), lmcs_salt_of(t));  // salted when the caller ran lmcs_salt_assign
   lmcs_compress_layers(c, t);
 }
 
@@ -561,7 +605,8 @@ bool lmcs_leaves_rangeable(mh_ctx* c, const std::vector<LdeMatrix>& mats) {
     if (m.log_n != mats[0].log_n || m.log_cosets != mats[0].log_cosets) return false;
   return true;
 }
-void lmcs_hash_leaves_range(mh_ctx* c, const std::vector<LdeMatrix>& mats, int lb, u64* digests, size_t q_begin, size_t q_count) {
+void lmcs_hash_leaves_range(mh_ctx* c, const std::vector<LdeMatrix>& mats, int lb, u64* digests, size_t q_begin, size_t q_count,
+                            const SaltArgs* salt) {
   MH_REQUIRE(lmcs_leaves_rangeable(c, mats), "internal: leaves cannot be hashed by ranges");
   LeafArgs a{};
   double bytes = 32.0 * (double)q_count;
@@ -581,14 +626,17 @@ void lmcs_hash_leaves_range(mh_ctx* c, const std::vector<LdeMatrix>& mats, int l
   MH_REQUIRE(q_count > 0 && q_begin + q_count <= ((size_t)1 << (a.log_n + lb)), "internal: leaf range out of bounds");
   ProfScope ps(c, "lmcs_leaf_absorb", bytes);
   const dim3 grid((unsigned)((q_count + LEAF_THREADS - 1) / LEAF_THREADS));
-  if (c->lmcs == MH_LMCS_BLAKE3) MH_LAUNCH(k_leaf_absorb_b3, grid, dim3(LEAF_THREADS), 0, c->stream, a);
+  if (salt && c->lmcs == MH_LMCS_BLAKE3) MH_LAUNCH(k_leaf_absorb_b3_salted, grid, dim3(LEAF_THREADS), 0, c->stream, a, *salt);
+  else if (salt) MH_LAUNCH(k_leaf_absorb_salted, grid, dim3(LEAF_THREADS), 0, c->stream, a, *salt);
+  else if (c->lmcs == MH_LMCS_BLAKE3) MH_LAUNCH(k_leaf_absorb_b3, grid, dim3(LEAF_THREADS), 0, c->stream, a);
   else MH_LAUNCH(k_leaf_absorb, grid, dim3(LEAF_THREADS), 0, c->stream, a);
 }
 
 // Leaf digests of a group of LDE matrices holding 2^lb cosets each (all cosets, or one rank's share
 // of them in the coset-sharded commit): digest slot j*N + r, N = tallest height.
-void lmcs_hash_leaves(mh_ctx* c, const std::vector<LdeMatrix>& mats, int lb, u64* digests) {
+void lmcs_hash_leaves(mh_ctx* c, const std::vector<LdeMatrix>& mats, int lb, u64* digests, const SaltArgs* salt) {
   MH_REQUIRE(!mats.empty(), "cannot commit empty batch");
+  MH_REQUIRE(!salt || (salt->n >= 1 && salt->n <= MH_MAX_SALT_ELEMS), "internal: bad salt width");
   for (size_t i = 1; i < mats.size(); i++)
     MH_REQUIRE(mats[i - 1].log_n <= mats[i].log_n, "matrices must be sorted by ascending height");
   // one launch per (height group, <=8 matrices) chained through a state buffer
@@ -630,7 +678,15 @@ void lmcs_hash_leaves(mh_ctx* c, const std::vector<LdeMatrix>& mats, int lb, u64
       bytes += 96.0 * leaves;
     }
     if (state_in) bytes += 96.0 * leaves;
-    {
+    const dim3 grid((unsigned)((leaves + LEAF_THREADS - 1) / LEAF_THREADS));
+    if (last && salt) {  // the salt meets the state of the last group only
+      ProfScope ps(c, "lmcs_leaf_absorb", bytes);
+      if (c->lmcs == MH_LMCS_RPO || c->lmcs == MH_LMCS_RPX)
+        MH_LAUNCH(k_leaf_absorb_alg_salted, grid, dim3(LEAF_THREADS), 0, c->stream, a, c->lmcs, *salt);
+      else if (c->lmcs == MH_LMCS_KECCAK) MH_LAUNCH(k_leaf_absorb_kk_salted, grid, dim3(LEAF_THREADS), 0, c->stream, a, *salt);
+      else if (c->lmcs == MH_LMCS_BLAKE3) MH_LAUNCH(k_leaf_absorb_b3_salted, grid, dim3(LEAF_THREADS), 0, c->stream, a, *salt);
+      else MH_LAUNCH(k_leaf_absorb_salted, grid, dim3(LEAF_THREADS), 0, c->stream, a, *salt);
+    } else {
       ProfScope ps(c, "lmcs_leaf_absorb", bytes);
       if (c->lmcs == MH_LMCS_RPO || c->lmcs == MH_LMCS_RPX)
         MH_LAUNCH(k_leaf_absorb_alg, dim3((unsigned)((leaves + LEAF_THREADS - 1) / LEAF_THREADS)), dim3(LEAF_THREADS), 0, c->stream, a,
@@ -687,6 +743,25 @@ OpenPlan lmcs_open_plan(const mh_tree* t, const std::vector<size_t>& idx, size_t
   const int lb = t->log_blowup, G = t->shard_logG;
   const int full_height = t->log_height + G;
   const size_t Bm = ((size_t)1 << lb) - 1;
+  // hiding LMCS: the opened leaves' salt rows (raw, unpadded, lmcs/proof.rs:108-121) follow each leaf's rows; they are regenerated into
+  // a buffer of the plan (the rows' kernel runs on the stream before the gather that reads it)
+  const int salt_n = t->salt.n;
+  if (salt_n) {
+    MH_REQUIRE(!distributed && G == 0, "internal: a salted tree cannot be sharded");
+    std::vector<u64> phys(idx.size());
+    for (size_t k = 0; k < idx.size(); k++) {
+      MH_REQUIRE(idx[k] < ((size_t)1 << full_height), "opening index out of range");
+      phys[k] = full_height ? (u64)bitrev32((u32)idx[k], full_height) : 0;
+    }
+    if (!idx.empty()) {
+      mh_ctx* c = t->ctx;
+      DevBuf rows(idx.size() * 8);
+      plan.salt_rows.alloc(idx.size() * (size_t)salt_n * 8);
+      c->h2d(rows.p, phys.data(), idx.size() * 8);
+      lmcs_salt_rows(c, t->salt, rows.u(), idx.size(), plan.salt_rows.u());
+    }
+  }
+  size_t leaf_k = 0;
   for (size_t i : idx) {
     MH_REQUIRE(i < ((size_t)1 << full_height), "opening index out of range");
     size_t j = i & Bm, r = i >> lb;
@@ -700,17 +775,19 @@ OpenPlan lmcs_open_plan(const mh_tree* t, const std::vector<size_t>& idx, size_t
         ptrs.push_back(mine ? t->fri_layer.u() + 2 * e : nullptr);
         ptrs.push_back(mine ? t->fri_layer.u() + 2 * e + 1 : nullptr);
       }
-      continue;
+    } else {
+      for (const LdeMatrix& m : t->mats) {
+        size_t N = (size_t)1 << m.log_n;
+        size_t rm = r & (N - 1);
+        const bool mine = i_contribute && j >= m.coset0 && j < m.coset0 + ((size_t)1 << m.log_cosets);
+        for (size_t cidx = 0; cidx < m.width; cidx++)
+          ptrs.push_back(mine ? m.lde.u() + (((cidx << m.log_cosets) + (j - m.coset0)) << m.log_n) + rm : nullptr);
+        size_t padded = (m.width + alignment - 1) / alignment * alignment;
+        for (size_t k = m.width; k < padded; k++) ptrs.push_back(nullptr);
+      }
     }
-    for (const LdeMatrix& m : t->mats) {
-      size_t N = (size_t)1 << m.log_n;
-      size_t rm = r & (N - 1);
-      const bool mine = i_contribute && j >= m.coset0 && j < m.coset0 + ((size_t)1 << m.log_cosets);
-      for (size_t cidx = 0; cidx < m.width; cidx++)
-        ptrs.push_back(mine ? m.lde.u() + (((cidx << m.log_cosets) + (j - m.coset0)) << m.log_n) + rm : nullptr);
-      size_t padded = (m.width + alignment - 1) / alignment * alignment;
-      for (size_t k = m.width; k < padded; k++) ptrs.push_back(nullptr);
-    }
+    for (int e = 0; e < salt_n; e++) ptrs.push_back(plan.salt_rows.u() + leaf_k * (size_t)salt_n + e);
+    leaf_k++;
   }
   plan.n_fields = ptrs.size() - plan.first;
   auto sib = lmcs_missing_siblings(idx, full_height);

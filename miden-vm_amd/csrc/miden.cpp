@@ -239,6 +239,10 @@ int mh_miden_air_blob(int which, const uint64_t** words_out, size_t* n_words) {
 static int prove_common(mh_ctx* ctx, const mh_miden* m, int hash_fn, const uint64_t* const* host_rm, const int* log_heights, mh_trace* const* traces,
                         const uint64_t* public_values, const uint64_t* aux_inputs, size_t n_aux_inputs, mh_proof** out) {
   if (!ctx || !m || m->ctx != ctx || !out) return MH_ERR_INVALID;
+  if (ctx->salt.n) {  // the statement provers pin the reference's (non-hiding) configurations
+    ctx->err = "mh_prove_miden is not available while the context's hiding LMCS is on (mh_ctx_set_salt)";
+    return MH_ERR_INVALID;
+  }
   mh_pcs_params prm;
   mh_miden_pcs_params(&prm);
   u64 pre[MH_MIDEN_PRE_OBSERVE_FELTS], state[12];

@@ -176,6 +176,10 @@ int mh_precompile_preprocessed_root(mh_precompile* s, int hash_fn, uint64_t root
 static int prove_common(mh_ctx* ctx, mh_precompile* s, int hash_fn, const uint64_t* const* host_rm, const int* log_heights, mh_trace* const* traces,
                         const uint64_t* public_root, mh_proof** out) {
   if (!ctx || !s || s->ctx != ctx || !out || !public_root || !lmcs_ok(hash_fn)) return MH_ERR_INVALID;
+  if (ctx->salt.n) {  // the statement provers pin the reference's (non-hiding) configurations
+    ctx->err = "mh_prove_precompile is not available while the context's hiding LMCS is on (mh_ctx_set_salt)";
+    return MH_ERR_INVALID;
+  }
   mh_pcs_params prm;
   mh_precompile_pcs_params(&prm);
   int rc = table_commitment(s, hash_fn, prm);

@@ -316,7 +316,7 @@ static bool commit_traces_pipelined(mh_ctx* c, mh_tree* t, const std::vector<con
     lmcs_alloc_layers(t, log_n + lb);
     for (size_t k = 0; k < groups.size(); k++) {
       HIP_CHECK(hipStreamWaitEvent(c->stream, done[k], 0));
-      lmcs_hash_leaves_range(c, t->mats, lb, lmcs_leaf_layer(t), groups[k].first * N, groups[k].second * N);
+      lmcs_hash_leaves_range(c, t->mats, lb, lmcs_leaf_layer(t), groups[k].first * N, groups[k].second * N, lmcs_salt_of(t));
     }
     lmcs_compress_layers(c, t);  // ends with a blocking copy of the root: both streams are idle when the coefficient buffers go back to the pool
   } catch (...) {
@@ -333,6 +333,7 @@ static bool commit_traces_pipelined(mh_ctx* c, mh_tree* t, const std::vector<con
 mh_tree* commit_traces(mh_ctx* c, const std::vector<const mh_trace*>& traces, int log_blowup) {
   std::unique_ptr<mh_tree> t(new mh_tree());
   t->ctx = c; t->log_blowup = log_blowup;
+  lmcs_salt_assign(c, t.get());  // hiding LMCS: this tree's number in the salt PRF (no-op with salt off)
   if (commit_traces_pipelined(c, t.get(), traces, log_blowup)) return t.release();
   for (const mh_trace* tr : traces) t->mats.push_back(lde_trace(c, tr, log_blowup));
   lmcs_build_tree(c, t.get());
@@ -342,6 +343,7 @@ mh_tree* commit_traces(mh_ctx* c, const std::vector<const mh_trace*>& traces, in
 // commit_traces of a sharded proof: this rank's cosets only, then the digest exchange.
 static mh_tree* commit_traces_dist(mh_ctx* c, const std::vector<const mh_trace*>& traces, int lb, const Dist& dist) {
   if (!dist.on()) return commit_traces(c, traces, lb);
+  MH_REQUIRE_NO_SALT(c, "a sharded commitment");
   std::unique_ptr<mh_tree> t(new mh_tree());
   t->ctx = c; t->log_blowup = lb;
   const size_t per = (size_t)1 << (lb - dist.logG);
@@ -421,6 +423,8 @@ struct mh_session {
              const u64* publics_in, size_t n_publics, const Dist& d) {
     c = ctx; pp = params; dist = d; n_airs = n;
     lmcs0 = c->lmcs;
+    salt0 = c->salt.n;
+    MH_REQUIRE(!(salt0 && dist.on()), "a sharded proof is not available while the context's hiding LMCS is on (mh_ctx_set_salt)");
     MH_REQUIRE(n_airs > 0 && n_airs <= 256, "need between 1 and 256 AIR instances");
     lb = pp.log_blowup;
     MH_REQUIRE(lb > 0 && lb <= 8, "log_blowup must be in 1..8");
@@ -489,6 +493,8 @@ struct mh_session {
                  "preprocessed tree was committed for a different sharding (use mh_commit_traces_sharded with the same communicator)");
       MH_REQUIRE((int)prep_tree->mats.size() == n_prep, "preprocessed tree holds matrices no AIR declares");
       MH_REQUIRE(prep_tree->lmcs == c->lmcs, "the preprocessed (setup) tree was committed with another LMCS hasher than this context's");
+      // one Lmcs for every tree of a proof (the reference's prover is generic over it): the verifier reads salt_elems felts per leaf
+      MH_REQUIRE(prep_tree->salt.n == c->salt.n, "the preprocessed (setup) tree was committed with another salt width than this context's (mh_ctx_set_salt)");
     }
     rounds = fri_num_rounds(pp, L);
     stage = 1;
@@ -513,9 +519,11 @@ struct mh_session {
   }
   size_t final_poly_len() const { return (size_t)1 << std::max(0, L - rounds * pp.log_folding_arity - lb); }
   int lmcs0 = 0;  // the context's LMCS hasher when the session began: one configuration per proof
+  int salt0 = 0;  // ... and its salt width (hiding LMCS)
   void expect(int s, const char* what) {
     MH_REQUIRE(stage == s, std::string("session call out of protocol order: ") + what);
     MH_REQUIRE(c->lmcs == lmcs0, "the context's LMCS hasher changed during the session");
+    MH_REQUIRE(c->salt.n == salt0, "the context's salt width changed during the session");
   }
 
   // ---- 1. main commitment ----
@@ -682,6 +690,7 @@ struct mh_session {
       lmcs_hash_leaves(c, quot_tree->mats, lbl, dig.u());
       lmcs_build_sharded(c, quot_tree.get(), dist, dig.u(), log_N);
     } else {
+      lmcs_salt_assign(c, quot_tree.get());
       lmcs_build_tree(c, quot_tree.get());
     }
     memcpy(root, quot_tree->root, 32);
@@ -812,7 +821,8 @@ struct mh_session {
       lmcs_build_sharded(c, t.get(), dist, dig.u(), log_rows - la);
     } else {
       lmcs_alloc_layers(t.get(), log_rows + cbits - la);
-      fri_leaf_hash(c, layer.u(), log_rows, cbits, la, lmcs_leaf_layer(t.get()));
+      lmcs_salt_assign(c, t.get());
+      fri_leaf_hash(c, layer.u(), log_rows, cbits, la, lmcs_leaf_layer(t.get()), lmcs_salt_of(t.get()));
       lmcs_compress_layers(c, t.get());
     }
     memcpy(root, t->root, 32);
@@ -1157,6 +1167,7 @@ struct mh_shard {
 int mh_shard_commit_leaves(mh_ctx* c, int n_traces, mh_trace* const* traces, int log_blowup, int rank, int world, mh_shard** out) {
   MH_TRY(c)
   MH_REQUIRE(c && traces && out && n_traces > 0, "null/empty argument");
+  MH_REQUIRE_NO_SALT(c, "mh_shard_commit_leaves");
   int lw = 0;
   while ((1 << lw) < world) lw++;
   MH_REQUIRE(world >= 1 && (1 << lw) == world && lw <= log_blowup, "world must be a power of two not larger than the blowup");
@@ -1191,6 +1202,7 @@ uint64_t* mh_shard_leaf_digests(mh_shard* s, size_t* n_digests) {
 int mh_shard_build_subtree(mh_ctx* c, mh_shard* s, const uint64_t* digests_device, uint64_t subroot[4]) {
   MH_TRY(c)
   MH_REQUIRE(c && s && digests_device && subroot, "null argument");
+  MH_REQUIRE_NO_SALT(c, "mh_shard_build_subtree");
   HIP_CHECK(hipSetDevice(c->device));
   std::unique_ptr<mh_tree> t(new mh_tree());
   t->ctx = c; t->log_blowup = s->log_blowup;
@@ -1265,6 +1277,7 @@ int mh_commit_traces_sharded(mh_ctx* c, const mh_comm* comm, int n_traces, mh_tr
                              uint64_t root[4]) {
   MH_TRY(c)
   MH_REQUIRE(c && comm && traces && out && n_traces > 0, "null/empty argument");
+  MH_REQUIRE_NO_SALT(c, "mh_commit_traces_sharded");
   MH_REQUIRE(log_blowup >= 0 && log_blowup <= 8, "bad log_blowup");
   MH_REQUIRE(comm->world >= 1 && (comm->world & (comm->world - 1)) == 0 && comm->rank >= 0 && comm->rank < comm->world,
              "world must be a power of two and 0 <= rank < world");
@@ -1335,6 +1348,7 @@ int mh_prove_sharded(mh_ctx* c, const mh_comm* comm, const mh_pcs_params* params
                      mh_aux_builder aux_builder, void* user, mh_proof** out) {
   MH_TRY(c)
   MH_REQUIRE(c && comm && params && airs && traces && challenger_state && out, "null argument");
+  MH_REQUIRE_NO_SALT(c, "mh_prove_sharded");
   MH_REQUIRE(public_values || !n_public_values, "null public values");
   MH_REQUIRE(pre_observe || !n_pre_observe, "null pre_observe");
   MH_REQUIRE(comm->world >= 1 && (comm->world & (comm->world - 1)) == 0 && comm->rank >= 0 && comm->rank < comm->world,

@@ -73,6 +73,8 @@ struct Reader {
 
 // the configuration being verified (MH_LMCS_*): set per call, per thread
 thread_local int t_hash = 0;
+// hiding LMCS (mh_verify_hiding): salt felts hinted after every opened leaf's rows, absorbed last; 0 = the plain LMCS
+thread_local int t_salt = 0;
 // aligned_len(w, lmcs.alignment()) (util/align.rs:7-13, proof.rs:268): the sponge's rate -- 8, or 17 for Keccak -- and 1 for the
 // chaining hasher of the Blake3 LMCS.  (The name dates from the Poseidon2 configuration.)
 size_t align8(size_t w) {
@@ -197,14 +199,20 @@ std::vector<std::vector<u64>> open_batch(Reader& rd, const Digest4& root, const 
                                          const std::vector<size_t>& idx, int depth) {
   size_t total = 0;
   for (size_t w : widths) total += w;
-  std::vector<std::vector<u64>> rows(idx.size(), std::vector<u64>(total));
+  // a hiding LMCS opens `rows + salt` (lmcs/proof.rs:108-137): the raw, unpadded salt follows the aligned rows and is absorbed as one
+  // more (short) matrix; the caller gets the rows alone
+  std::vector<size_t> hashed(widths);
+  if (t_salt) hashed.push_back((size_t)t_salt);
+  std::vector<std::vector<u64>> rows(idx.size(), std::vector<u64>(total + (size_t)t_salt));
   std::vector<std::pair<size_t, Digest4>> level;
   for (size_t q = 0; q < idx.size(); q++)
     for (auto& x : rows[q]) x = rd.hint_field();
   {
-    const std::vector<Digest4> leaves = leaf_digests(rows, widths);
+    const std::vector<Digest4> leaves = leaf_digests(rows, hashed);
     for (size_t q = 0; q < idx.size(); q++) level.push_back({idx[q], leaves[q]});
   }
+  if (t_salt)
+    for (auto& r : rows) r.resize(total);
   for (int d = depth; d > 0; d--) {
     std::vector<size_t> parents;
     std::vector<std::pair<Digest4, Digest4>> pairs;  // (left, right) of every parent of this level, in stream order
@@ -587,7 +595,7 @@ void verify_impl(const mh_pcs_params& pp, const std::vector<DagIR>& airs, const 
 
 }  // namespace
 
-static int verify_entry(int lmcs, const mh_pcs_params* params, int n_airs, const uint64_t* const* air_blobs, const size_t* air_blob_words,
+static int verify_entry(int lmcs, int salt_elems, const mh_pcs_params* params, int n_airs, const uint64_t* const* air_blobs, const size_t* air_blob_words,
                         const uint8_t* log_trace_heights, const uint64_t* public_values, size_t n_public_values,
                         const uint64_t challenger_state[12], const uint64_t* pre_observe, size_t n_pre_observe, const uint64_t* fields,
                         size_t n_fields, const uint64_t* commitments, size_t n_commitments, const uint64_t* preprocessed_root,
@@ -612,7 +620,9 @@ static int verify_entry(int lmcs, const mh_pcs_params* params, int n_airs, const
       lhs.push_back(log_trace_heights[i]);
     }
     MH_REQUIRE(lmcs >= MH_LMCS_POSEIDON2 && lmcs <= MH_LMCS_RPX, "unknown LMCS hasher id");
+    MH_REQUIRE(salt_elems >= 0 && salt_elems <= MH_MAX_SALT_ELEMS, "salt_elems must be in 0..MH_MAX_SALT_ELEMS");
     t_hash = lmcs;
+    t_salt = salt_elems;
     Reader rd;
     rd.ch.hash = lmcs;
     rd.ch.init_from_state(challenger_state);
@@ -638,7 +648,7 @@ int mh_verify(const mh_pcs_params* params, int n_airs, const uint64_t* const* ai
               const uint8_t* log_trace_heights, const uint64_t* public_values, size_t n_public_values, const uint64_t challenger_state[12],
               const uint64_t* pre_observe, size_t n_pre_observe, const uint64_t* fields, size_t n_fields, const uint64_t* commitments,
               size_t n_commitments, const uint64_t* preprocessed_root, uint64_t digest[4], char* err, size_t err_cap) {
-  return verify_entry(MH_LMCS_POSEIDON2, params, n_airs, air_blobs, air_blob_words, log_trace_heights, public_values, n_public_values, challenger_state,
+  return verify_entry(MH_LMCS_POSEIDON2, 0, params, n_airs, air_blobs, air_blob_words, log_trace_heights, public_values, n_public_values, challenger_state,
                       pre_observe, n_pre_observe, fields, n_fields, commitments, n_commitments, preprocessed_root, nullptr, nullptr, digest,
                       err, err_cap);
 }
@@ -647,7 +657,7 @@ int mh_verify_ex(const mh_pcs_params* params, int n_airs, const uint64_t* const*
                  const uint64_t challenger_state[12], const uint64_t* pre_observe, size_t n_pre_observe, const uint64_t* fields,
                  size_t n_fields, const uint64_t* commitments, size_t n_commitments, const uint64_t* preprocessed_root,
                  mh_external_assertions external, void* external_user, uint64_t digest[4], char* err, size_t err_cap) {
-  return verify_entry(MH_LMCS_POSEIDON2, params, n_airs, air_blobs, air_blob_words, log_trace_heights, public_values, n_public_values,
+  return verify_entry(MH_LMCS_POSEIDON2, 0, params, n_airs, air_blobs, air_blob_words, log_trace_heights, public_values, n_public_values,
                       challenger_state, pre_observe, n_pre_observe, fields, n_fields, commitments, n_commitments, preprocessed_root,
                       external, external_user, digest, err, err_cap);
 }
@@ -656,7 +666,18 @@ int mh_verify_lmcs(int lmcs, const mh_pcs_params* params, int n_airs, const uint
                    const uint64_t challenger_state[12], const uint64_t* pre_observe, size_t n_pre_observe, const uint64_t* fields,
                    size_t n_fields, const uint64_t* commitments, size_t n_commitments, const uint64_t* preprocessed_root,
                    mh_external_assertions external, void* external_user, uint64_t digest[4], char* err, size_t err_cap) {
-  return verify_entry(lmcs, params, n_airs, air_blobs, air_blob_words, log_trace_heights, public_values, n_public_values,
+  return verify_entry(lmcs, 0, params, n_airs, air_blobs, air_blob_words, log_trace_heights, public_values, n_public_values,
+                      challenger_state, pre_observe, n_pre_observe, fields, n_fields, commitments, n_commitments, preprocessed_root,
+                      external, external_user, digest, err, err_cap);
+}
+// mh_verify_lmcs for a proof made under a hiding LMCS (mh_ctx_set_salt): every opened leaf of every tree -- preprocessed, main, aux,
+// quotient, each FRI round -- carries salt_elems salt felts behind its rows.  salt_elems = 0 is mh_verify_lmcs.
+int mh_verify_hiding(int lmcs, int salt_elems, const mh_pcs_params* params, int n_airs, const uint64_t* const* air_blobs,
+                     const size_t* air_blob_words, const uint8_t* log_trace_heights, const uint64_t* public_values, size_t n_public_values,
+                     const uint64_t challenger_state[12], const uint64_t* pre_observe, size_t n_pre_observe, const uint64_t* fields,
+                     size_t n_fields, const uint64_t* commitments, size_t n_commitments, const uint64_t* preprocessed_root,
+                     mh_external_assertions external, void* external_user, uint64_t digest[4], char* err, size_t err_cap) {
+  return verify_entry(lmcs, salt_elems, params, n_airs, air_blobs, air_blob_words, log_trace_heights, public_values, n_public_values,
                       challenger_state, pre_observe, n_pre_observe, fields, n_fields, commitments, n_commitments, preprocessed_root,
                       external, external_user, digest, err, err_cap);
 }
