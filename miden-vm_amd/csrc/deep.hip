@@ -12,6 +12,20 @@
 // produced in-register (4 points x 2 OOD points per lane, one Fermat inversion per 8 norms) instead
 // of the reference's 268 MB point-quotient table.
 // Roofline: HBM-bound stream (8 B per LDE felt read once, 16 B per point written).
+//
+// One coset is enough.  Let N = the max trace height and x range over the LDE domain g*<w_K>, K = B*N.
+//  * A committed column of height N is a polynomial f of degree < N.  A column of a shorter matrix (height n = N/L) is stored on its own
+//    LDE domain g^L*<w_(K/L)> and read here at row r & (n - 1) of coset j: that is F(x) = f(x^L) on the max domain, deg F < n*L = N.
+//  * neg(x) = sum_i -alpha^(W-1-i) F_i(x) is therefore a polynomial of degree < N (over EF), and f_red(z_k) = sum_i alpha^(W-1-i) F_i(z_k)
+//    = -neg(z_k): the OOD vector holds f_i(z^L) and f_i((z*w_N)^L) = f_i(z^L * w_n) -- the lifted columns' values at z_0 = z and at
+//    z_1 = z_next = z*w_N, the next row of every height at once.
+//  * So each numerator f_red(z_k) + neg(x) vanishes at x = z_k, each division by (z_k - x) is exact, and
+//    Q(x) = sum_k beta^k (f_red(z_k) + neg(x)) / (z_k - x) is a polynomial of degree <= N - 2.
+// N values determine it: k_deep_assemble<true> computes Q on the rank's first stored coset x_0*H only (1/B of the reads and of the
+// mads), as two base-field planes, and lde_columns -- the call the quotient chunks already go through, input shift != 1 -- evaluates it
+// on every stored coset x_j*H; k_deep_interleave pairs the planes up for the FRI layer.  Exact arithmetic, canonical outputs: the
+// layer is felt for felt the one k_deep_assemble<false> writes on all B cosets (MH_DEEP_ALL_COSETS=1; also the path for B = 1 and
+// for N < 4).  A rank of a sharded proof extends from its own first coset: nothing is exchanged.
 #include "gl.cuh"
 #include "kernels.hpp"
 
@@ -208,9 +222,12 @@ struct DeepArgs {
   const u64* tw;                  // w_N^k
   const u64* coset_x;             // [B] g*w_K^j
   e2 z0, z1, fred0, fred1, beta;
-  u64* out;                       // EF pairs, coset-major [B][N]
+  u64* out;                       // EF pairs, coset-major [B][N]; PLANES: [2][N], c0 plane then c1 plane (grid.y = 1)
 };
 
+// PLANES = false: every stored coset (grid.y = B), EF pairs.  PLANES = true: the rank's first stored coset only (grid.y = 1), as the
+// two base-field columns that lde_columns extends to the other cosets (header, "One coset is enough").
+template <bool PLANES>
 __global__ __launch_bounds__(256) void k_deep_assemble(DeepArgs a) {
   const size_t N = (size_t)1 << a.log_n;
   const size_t j = blockIdx.y;
@@ -322,16 +339,30 @@ __global__ __launch_bounds__(256) void k_deep_assemble(DeepArgs a) {
     if (r[k] < N) {
       e2 v = e2_mul(qinv[2 * k], e2_add(a.fred0, neg[k]));
       v = e2_add(v, e2_mul(e2_mul(a.beta, qinv[2 * k + 1]), e2_add(a.fred1, neg[k])));
-      ulonglong2* o = reinterpret_cast<ulonglong2*>(a.out + 2 * ((j << a.log_n) + r[k]));
-      *o = make_ulonglong2(v.c0, v.c1);
+      if constexpr (PLANES) {
+        a.out[r[k]] = v.c0;
+        a.out[N + r[k]] = v.c1;
+      } else {
+        ulonglong2* o = reinterpret_cast<ulonglong2*>(a.out + 2 * ((j << a.log_n) + r[k]));
+        *o = make_ulonglong2(v.c0, v.c1);
+      }
     }
   }
 }
 
+// planes [2][n] (c0 plane, c1 plane; n = B * N points, coset-major) -> EF pairs [n], one point per lane
+__global__ __launch_bounds__(256) void k_deep_interleave(const u64* __restrict__ planes, size_t n, u64* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  *reinterpret_cast<ulonglong2*>(out + 2 * i) = make_ulonglong2(planes[i], planes[n + i]);
+}
+
 // mats: every committed matrix in transcript order (main.., aux.., quotient); negc: -alpha^(W-1-i)
 // per ALIGNED column index.  out: EF pairs coset-major [B][N].
+// one_coset: assemble on the first stored coset only and extend to the others by a coset LDE of the two planes (the caller asks for
+// it only with B >= 2 and log_n >= DEEP_ONE_COSET_MIN_LOG_N); the values written are the same, felt for felt.
 void deep_assemble(mh_ctx* c, const std::vector<const LdeMatrix*>& mats, const std::vector<u32>& coef_off, int log_n, int log_blowup,
-                   const std::vector<e2>& negc, e2 z0, e2 z1, e2 fred0, e2 fred1, e2 beta, u64* out) {
+                   const std::vector<e2>& negc, e2 z0, e2 z1, e2 fred0, e2 fred1, e2 beta, u64* out, bool one_coset) {
   MH_REQUIRE(mats.size() <= (size_t)DEEP_MAX_MATS, "too many committed matrices for one DEEP pass");
   const int lbl = mats[0]->log_cosets;  // cosets stored on this rank (all matrices alike)
   const size_t coset0 = mats[0]->coset0;
@@ -356,19 +387,38 @@ void deep_assemble(mh_ctx* c, const std::vector<const LdeMatrix*>& mats, const s
     c->h2d(one.p, &v, 8);
     tw = one.u();
   }
+  MH_REQUIRE(!one_coset || (lbl >= 1 && log_n >= DEEP_ONE_COSET_MIN_LOG_N), "internal: one-coset DEEP assemble needs two cosets to extend to");
+  const size_t Ba = one_coset ? 1 : B;  // cosets the assemble kernel runs on
   DeepArgs a{};
-  double bytes = 16.0 * N * B;
+  double bytes = 16.0 * N * Ba;
   for (size_t i = 0; i < mats.size(); i++) {
     a.m[i] = DeepMat{mats[i]->lde.u(), (u32)mats[i]->width, coef_off[i], mats[i]->log_n};
-    bytes += 8.0 * (double)mats[i]->width * (double)(((size_t)1 << mats[i]->log_n) << lbl);
+    bytes += 8.0 * (double)mats[i]->width * (double)(((size_t)1 << mats[i]->log_n) * Ba);
   }
   a.n_mats = (int)mats.size();
   a.log_n = log_n; a.log_blowup = lbl;
   a.negc = dblob.u(); a.tw = tw; a.coset_x = dblob.u() + o_cx;
   a.z0 = z0; a.z1 = z1; a.fred0 = fred0; a.fred1 = fred1; a.beta = beta; a.out = out;
+  const dim3 grid((unsigned)((N + 256 * DEEP_PTS - 1) / (256 * DEEP_PTS)), (unsigned)Ba);
+  if (!one_coset) {
+    ProfScope ps(c, "deep_assemble", bytes);
+    MH_LAUNCH(k_deep_assemble<false>, grid, dim3(256), 0, c->stream, a);
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    return;
+  }
+  DevBuf planes(2 * N * 8), scratch(2 * N * 8), ext(2 * B * N * 8);
+  a.out = planes.u();
   {
     ProfScope ps(c, "deep_assemble", bytes);
-    MH_LAUNCH(k_deep_assemble, dim3((unsigned)((N + 256 * DEEP_PTS - 1) / (256 * DEEP_PTS)), (unsigned)B), dim3(256), 0, c->stream, a);
+    MH_LAUNCH(k_deep_assemble<true>, grid, dim3(256), 0, c->stream, a);
+  }
+  {
+    // Q on x_0 * H -> Q on x_j * H for every stored coset, in their stored order (coset 0 comes out again: the same values);
+    // 16 N read, the [2][B][N] planes written, read again and written as pairs
+    ProfScope ps(c, "deep_extend", 16.0 * N + 3.0 * 16.0 * N * B);
+    const std::vector<u64> shifts(blob.begin() + o_cx, blob.begin() + o_cx + B);
+    lde_columns(c, planes.u(), 2, log_n, shifts[0], shifts, ext.u(), scratch.u());
+    MH_LAUNCH(k_deep_interleave, dim3((unsigned)((B * N + 255) / 256)), dim3(256), 0, c->stream, ext.u(), B * N, out);
   }
   HIP_CHECK(hipStreamSynchronize(c->stream));
 }

@@ -172,8 +172,11 @@ struct OodJob {
 void deep_ood_eval_batch(mh_ctx* c, std::vector<OodJob>& jobs, int log_blowup);
 void deep_ood_eval_matrix(mh_ctx* c, const LdeMatrix& m, int log_blowup, e2 y0, e2 y1, std::vector<e2>& out0, std::vector<e2>& out1,
                           size_t col_begin = 0, size_t col_end = (size_t)-1);
+// one_coset: assemble on the rank's first stored coset and extend to the others with lde_columns (needs >= 2 stored cosets and
+// log_n >= DEEP_ONE_COSET_MIN_LOG_N); false: the assemble kernel runs on every stored coset.  The layer is the same either way.
+static constexpr int DEEP_ONE_COSET_MIN_LOG_N = 2;
 void deep_assemble(mh_ctx* c, const std::vector<const LdeMatrix*>& mats, const std::vector<uint32_t>& coef_off, int log_n, int log_blowup,
-                   const std::vector<e2>& negc, e2 z0, e2 z1, e2 fred0, e2 fred1, e2 beta, u64* out);
+                   const std::vector<e2>& negc, e2 z0, e2 z1, e2 fred0, e2 fred1, e2 beta, u64* out, bool one_coset);
 // ---- fri.hip -----------------------------------------------------------------------------------
 void fri_leaf_hash(mh_ctx* c, const u64* ev, int log_rows, int cbits, int log_arity, u64* digests, const SaltArgs* salt = nullptr);
 // cbits = coset bits stored locally, cbits_global / coset0 locate them in the whole layer

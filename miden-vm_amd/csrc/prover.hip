@@ -779,7 +779,11 @@ struct mh_session {
       pw = e2_mul(pw, alpha_d);
     }
     layer.alloc((N << lbl) * 16);
-    deep_assemble(c, mats, coef_off, log_N, lb, negc, z, z_next, fred0, fred1, beta_d, layer.u());
+    // Q has degree < N, so one coset determines it: assemble there, extend by LDE (deep.hip).  MH_DEEP_ALL_COSETS=1 keeps the
+    // assemble kernel on every coset (the reference path of tests/test_gpu_deep_one_coset.py); read per call, never cached.
+    const char* all_env = getenv("MH_DEEP_ALL_COSETS");
+    const bool one_coset = !(all_env && atoi(all_env)) && lbl >= 1 && log_N >= DEEP_ONE_COSET_MIN_LOG_N;
+    deep_assemble(c, mats, coef_off, log_N, lb, negc, z, z_next, fred0, fred1, beta_d, layer.u(), one_coset);
     // cbits = coset bits of the whole layer, cb_loc = those stored on this rank (cosets fri_c0 ..)
     log_rows = log_N; cbits = lb; cb_loc = lbl; fri_c0 = coset0;
     sharded = dist.on();
