@@ -151,6 +151,8 @@ unsafe extern "C" {
     pub fn mh_host_free(p: *mut c_void);
     // ---- commitments ----
     pub fn mh_commit_traces(ctx: *mut mh_ctx, n_traces: c_int, traces: *const *mut mh_trace, log_blowup: c_int, out: *mut *mut mh_tree, root: *mut u64) -> c_int;
+    /// host only (no context, no GPU): mh_commit_traces' root from row-major host matrices -- the verifier's way to a preprocessed_root
+    pub fn mh_commit_host(lmcs: c_int, n_mats: c_int, rowmajor: *const *const u64, log_heights: *const u8, widths: *const usize, log_blowup: c_int, root: *mut u64, err: *mut c_char, err_cap: usize) -> c_int;
     pub fn mh_tree_free(t: *mut mh_tree);
     pub fn mh_tree_root(t: *const mh_tree, root: *mut u64) -> c_int;
     pub fn mh_tree_log_height(t: *const mh_tree) -> c_int;
@@ -216,9 +218,12 @@ unsafe extern "C" {
     pub fn mh_precompile_free(s: *mut mh_precompile);
     pub fn mh_precompile_air_blob(which: c_int, lookup: c_int, words_out: *mut *const u64, n_words: *mut usize) -> c_int;
     pub fn mh_precompile_preprocessed_root(s: *mut mh_precompile, hash_fn: c_int, root: *mut u64) -> c_int;
+    /// host only: the byte-pair table's setup commitment derived from the table (cached per hash function)
+    pub fn mh_precompile_setup_root(hash_fn: c_int, root: *mut u64) -> c_int;
     pub fn mh_precompile_pre_observe(p: *const mh_pcs_params, preprocessed_root: *const u64, public_root: *const u64, out: *mut u64) -> c_int;
     pub fn mh_prove_precompile(ctx: *mut mh_ctx, s: *mut mh_precompile, hash_fn: c_int, mains_rowmajor: *const *const u64, log_heights: *const c_int, public_root: *const u64, out: *mut *mut mh_proof) -> c_int;
     pub fn mh_prove_precompile_traces(ctx: *mut mh_ctx, s: *mut mh_precompile, hash_fn: c_int, traces: *const *mut mh_trace, public_root: *const u64, out: *mut *mut mh_proof) -> c_int;
+    /// preprocessed_root: null = derive it (mh_precompile_setup_root); non-null = checked against the derived root first
     pub fn mh_verify_precompile(hash_fn: c_int, preprocessed_root: *const u64, public_root: *const u64, proof_bytes: *const u8, n_bytes: usize, digest: *mut u64, err: *mut c_char, err_cap: usize) -> c_int;
     pub fn mh_proof_deserialize(bytes: *const u8, len: usize, out: *mut *mut mh_proof) -> c_int;
     pub fn mh_trace_upload_sharded(ctx: *mut mh_ctx, comm: *const mh_comm, rowmajor: *const u64, log_n: c_int, width: usize, out: *mut *mut mh_trace) -> c_int;

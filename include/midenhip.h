@@ -157,6 +157,16 @@ void mh_blake3(const uint8_t* data, size_t n, uint8_t out32[32]);
  * aligned LMCS tree (Lmcs::build_aligned_tree, lmcs/config.rs:125-137).  root = 4 felts. */
 int mh_commit_traces(mh_ctx* ctx, int n_traces, mh_trace* const* traces, int log_blowup, mh_tree** out,
                      uint64_t root[4]);
+/* mh_commit_traces' root on the CPU: HOST ONLY (no context, no HIP call), for verifiers and setup.  The root of an AIR's preprocessed
+ * matrices is part of the statement a verifier checks (the preprocessed_root of mh_verify*): a verifier box has no GPU and derives it
+ * here from the matrices it knows, instead of being told it by the prover.  No prover entry calls this; proving has no CPU path.
+ * rowmajor[i]: matrix i, row-major, 2^log_heights[i] rows of widths[i] cells (any uint64_t, reduced mod p as every upload path does),
+ * in proof order = ascending height.  root = exactly what mh_commit_traces returns for the same matrices in the same order on a
+ * context set to `lmcs` (MH_LMCS_*) with salt off, byte-hash roots packed as by mh_tree_root.  Uses up to 16 threads.
+ * MH_ERR_INVALID + a reason in err (may be NULL): a null pointer, n_mats < 1, a zero width, log_blowup outside 0..8,
+ * log_heights[i] + log_blowup > 32, descending heights, an unknown lmcs. */
+int mh_commit_host(int lmcs, int n_mats, const uint64_t* const* rowmajor, const uint8_t* log_heights, const size_t* widths,
+                   int log_blowup, uint64_t root[4], char* err, size_t err_cap);
 void mh_tree_free(mh_tree* t);
 int mh_tree_root(const mh_tree* t, uint64_t root[4]);
 int mh_tree_log_height(const mh_tree* t);
@@ -492,8 +502,12 @@ int mh_precompile_load(mh_ctx* ctx, mh_precompile** out);
 void mh_precompile_free(mh_precompile* s);
 /* the embedded blobs, for a caller that drives the generic entry points itself: lookup = 0 the constraint DAG, 1 the lookup program */
 int mh_precompile_air_blob(int which, int lookup, const uint64_t** words_out, size_t* n_words);
-/* the setup commitment of the byte-pair table under hash_fn (made on first use, then cached in `s`): what a verifier must be given */
+/* the setup commitment of the byte-pair table under hash_fn, made on the device (on first use, then cached in `s`) */
 int mh_precompile_preprocessed_root(mh_precompile* s, int hash_fn, uint64_t root[4]);
+/* the same root derived on the HOST from the table itself (mh_commit_host at mh_precompile_pcs_params().log_blowup; the reference's
+ * session/preprocessed_cache.rs): no context, no GPU.  Derived once per hash function and process (0.3 - 7 s by hasher), then kept; safe to
+ * call from several threads.  This is the verifier's copy of the verifying key: mh_verify_precompile pins it. */
+int mh_precompile_setup_root(int hash_fn, uint64_t root[4]);
 int mh_precompile_pre_observe(const mh_pcs_params* p, const uint64_t preprocessed_root[4], const uint64_t public_root[4],
                               uint64_t out[MH_PRECOMPILE_PRE_OBSERVE_FELTS]);
 int mh_prove_precompile(mh_ctx* ctx, mh_precompile* s, int hash_fn, const uint64_t* const mains_rowmajor[MH_PRECOMPILE_NUM_AIRS],
@@ -502,9 +516,11 @@ int mh_prove_precompile(mh_ctx* ctx, mh_precompile* s, int hash_fn, const uint64
 int mh_prove_precompile_traces(mh_ctx* ctx, mh_precompile* s, int hash_fn, mh_trace* const traces[MH_PRECOMPILE_NUM_AIRS],
                                const uint64_t public_root[4], mh_proof** out);
 /* `verify_stark` (session/prove.rs:365-383, 386-425): StarkProofData bytes -> MH_OK + the transcript digest, or MH_ERR_INVALID + reason.
- * Host only (no context, no GPU); preprocessed_root = mh_precompile_preprocessed_root of a prover-side context (the reference's
- * verifier recomputes it from the table; this library has no CPU path for an LDE + Merkle commitment, by design). */
-int mh_verify_precompile(int hash_fn, const uint64_t preprocessed_root[4], const uint64_t public_root[4], const uint8_t* proof_bytes,
+ * Host only (no context, no GPU).  The setup commitment of the byte-pair table is part of the statement and the verifier derives it
+ * itself (mh_precompile_setup_root, as the reference's verifier recomputes it from the table): preprocessed_root = NULL is the normal
+ * call.  A non-NULL preprocessed_root is CHECKED against the derived root before any proof byte is read; one that differs -- a root
+ * forwarded from a prover who committed another table -- is MH_ERR_INVALID with a reason that names the setup commitment. */
+int mh_verify_precompile(int hash_fn, const uint64_t preprocessed_root[4] /* or NULL */, const uint64_t public_root[4], const uint8_t* proof_bytes,
                          size_t n_bytes, uint64_t digest[4], char* err, size_t err_cap);
 
 /* ---- the Miden VM statement: prove_stark's own shape (prover/src/lib.rs:317-355) --------------------------------------------------

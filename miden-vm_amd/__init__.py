@@ -40,6 +40,7 @@ EXPORTS = [
     "mh_check_constraints", "mh_check_miden", "mh_check_miden_traces", "mh_check_precompile", "mh_check_precompile_traces",
     "mh_check_balance", "mh_check_balance_miden", "mh_check_balance_miden_traces", "mh_check_balance_precompile", "mh_check_balance_precompile_traces",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
+    "mh_commit_host", "mh_precompile_setup_root",
 ]
 
 MH_MAX_SALT_ELEMS = 8  # mh_ctx_set_salt: the largest salt width of the hiding LMCS
@@ -523,6 +524,26 @@ def commit_traces(ctx, traces, log_blowup):
 
 # ---- the whole proof (miden_prover::prove_stark -> lifted_stark::prover::prove) ---------------------
 AUX_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, u64p, u64p, u64p)
+
+
+def commit_host(mats, log_blowup, lmcs="poseidon2"):
+    """mh_commit_host (host only, no context): the root commit_traces(ctx, mats, log_blowup).root() gives on a context set to `lmcs`,
+    from row-major host matrices in proof order (ascending height) -- how a verifier derives an AIR's preprocessed_root."""
+    lib = load_library()
+    hs = [np.ascontiguousarray(m, dtype=np.uint64) for m in mats]
+    n = len(hs)
+    if n < 1 or any(m.ndim != 2 or m.shape[0] < 1 or m.shape[0] & (m.shape[0] - 1) for m in hs):
+        raise MidenHipError("commit_host: at least one matrix, each 2-D with a power-of-two number of rows")
+    ptrs = (u64p * n)(*[_ptr(m) for m in hs])
+    lhs = (C.c_uint8 * n)(*[int(m.shape[0]).bit_length() - 1 for m in hs])
+    ws = (C.c_size_t * n)(*[m.shape[1] for m in hs])
+    root, err = np.zeros(4, dtype=np.uint64), C.create_string_buffer(512)
+    lib.mh_commit_host.argtypes = [C.c_int, C.c_int, C.POINTER(u64p), C.POINTER(C.c_uint8), C.POINTER(C.c_size_t), C.c_int, u64p, C.c_char_p,
+                                   C.c_size_t]
+    rc = lib.mh_commit_host(Ctx.LMCS[lmcs], n, ptrs, lhs, ws, int(log_blowup), _ptr(root), err, 512)
+    if rc != 0:
+        raise MidenHipError(f"mh_commit_host failed ({rc}): {err.value.decode()}")
+    return root
 
 
 class PcsParams(C.Structure):
@@ -1098,14 +1119,29 @@ class Precompile:
             pass
 
 
-def verify_precompile(preprocessed_root, public_root, proof_bytes, hash_fn="poseidon2"):
-    """mh_verify_precompile (host only): StarkProofData bytes of a precompile-session proof -> (True, digest) or (False, reason)."""
+def precompile_setup_root(hash_fn="poseidon2"):
+    """mh_precompile_setup_root (host only): the byte-pair table's setup commitment under `hash_fn`, derived from the table on the CPU
+    (once per hash function and process) -- equal to Precompile.preprocessed_root(hash_fn) of a prover's context."""
     lib = load_library()
-    pr, root = _arr([int(x) for x in preprocessed_root]), _arr([int(x) for x in public_root])
+    root = np.zeros(4, dtype=np.uint64)
+    lib.mh_precompile_setup_root.argtypes = [C.c_int, u64p]
+    rc = lib.mh_precompile_setup_root(Ctx.LMCS[hash_fn], _ptr(root))
+    if rc != 0:
+        raise MidenHipError(f"mh_precompile_setup_root failed ({rc})")
+    return root
+
+
+def verify_precompile(preprocessed_root, public_root, proof_bytes, hash_fn="poseidon2"):
+    """mh_verify_precompile (host only): StarkProofData bytes of a precompile-session proof -> (True, digest) or (False, reason).
+    preprocessed_root=None (the verifier's normal call): the setup commitment is derived from the byte-pair table; a root that is given
+    is checked against the derived one before the proof is read."""
+    lib = load_library()
+    pr = None if preprocessed_root is None else _arr([int(x) for x in preprocessed_root])
+    root = _arr([int(x) for x in public_root])
     buf = (C.c_uint8 * max(1, len(proof_bytes))).from_buffer_copy(bytes(proof_bytes) or b"\0")
     digest, err = np.zeros(4, dtype=np.uint64), C.create_string_buffer(512)
     lib.mh_verify_precompile.argtypes = [C.c_int, u64p, u64p, C.c_void_p, C.c_size_t, u64p, C.c_char_p, C.c_size_t]
-    rc = lib.mh_verify_precompile(Ctx.LMCS[hash_fn], _ptr(pr), _ptr(root), buf, len(proof_bytes), _ptr(digest), err, 512)
+    rc = lib.mh_verify_precompile(Ctx.LMCS[hash_fn], None if pr is None else _ptr(pr), _ptr(root), buf, len(proof_bytes), _ptr(digest), err, 512)
     return (True, digest) if rc == 0 else (False, err.value.decode())
 
 

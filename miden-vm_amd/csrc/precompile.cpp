@@ -23,6 +23,7 @@
 #include "kernels.hpp"
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -71,6 +72,17 @@ const Blobs& blobs() {
 
 bool lmcs_ok(int h) { return h >= 0 && h < N_LMCS; }
 
+// `preprocessed_table` (byte_pair_lut.rs:262-277): every (a, b) in lexicographic order, row a << 8 | b = (a, b, !a & b, a ^ b).
+// The one definition of the table: what the prover uploads (mh_precompile_load) and what the verifier commits (mh_precompile_setup_root).
+std::vector<u64> byte_pair_table() {
+  std::vector<u64> tab((size_t)4 << LOG_BPL_HEIGHT);
+  for (u64 idx = 0; idx < ((u64)1 << LOG_BPL_HEIGHT); idx++) {
+    const u64 a = idx >> 8, bb = idx & 0xff;
+    tab[4 * idx] = a; tab[4 * idx + 1] = bb; tab[4 * idx + 2] = (~a & 0xff) & bb; tab[4 * idx + 3] = a ^ bb;
+  }
+  return tab;
+}
+
 }  // namespace
 
 struct mh_precompile {
@@ -101,6 +113,10 @@ int mh_precompile_air_blob(int which, int lookup, const uint64_t** words_out, si
 int mh_precompile_pre_observe(const mh_pcs_params* p, const uint64_t preprocessed_root[4], const uint64_t public_root[4],
                               uint64_t out[MH_PRECOMPILE_PRE_OBSERVE_FELTS]) {
   if (!p || !preprocessed_root || !public_root || !out) return MH_ERR_INVALID;
+  // the values are observed as field elements and the arity as 1 << log_folding_arity: only what a verifier accepts (csrc/verifier.cpp) is framed
+  if (p->log_folding_arity < 1 || p->log_folding_arity > 3 || p->log_blowup < 0 || p->log_blowup > 32 || p->log_final_degree < 0 ||
+      p->log_final_degree > 32 || p->num_queries < 0 || p->query_pow_bits < 0 || p->deep_pow_bits < 0 || p->folding_pow_bits < 0)
+    return MH_ERR_INVALID;
   size_t k = 0;
   // observe_protocol_params (stark_config.rs, as air/src/config.rs:188-198)
   const u64 head[8] = {(u64)p->num_queries, (u64)p->query_pow_bits, (u64)p->deep_pow_bits, (u64)p->folding_pow_bits, (u64)p->log_blowup,
@@ -137,12 +153,7 @@ int mh_precompile_load(mh_ctx* ctx, mh_precompile** out) {
     if (rc == MH_OK) rc = mh_air_attach_lookup(s->airs[i], s->lookups[i]);
     if (rc != MH_OK) return rc;
   }
-  // `preprocessed_table` (byte_pair_lut.rs:262-277): every (a, b) in lexicographic order, row a << 8 | b = (a, b, !a & b, a ^ b)
-  std::vector<u64> tab((size_t)4 << LOG_BPL_HEIGHT);
-  for (u64 idx = 0; idx < ((u64)1 << LOG_BPL_HEIGHT); idx++) {
-    const u64 a = idx >> 8, bb = idx & 0xff;
-    tab[4 * idx] = a; tab[4 * idx + 1] = bb; tab[4 * idx + 2] = (~a & 0xff) & bb; tab[4 * idx + 3] = a ^ bb;
-  }
+  const std::vector<u64> tab = byte_pair_table();
   const int rc = mh_trace_upload(ctx, tab.data(), LOG_BPL_HEIGHT, 4, &s->table);
   if (rc != MH_OK) return rc;
   *out = s.release();
@@ -217,7 +228,34 @@ int mh_prove_precompile(mh_ctx* ctx, mh_precompile* s, int hash_fn, const uint64
 int mh_prove_precompile_traces(mh_ctx* ctx, mh_precompile* s, int hash_fn, mh_trace* const traces[MH_PRECOMPILE_NUM_AIRS],
                                const uint64_t public_root[4], mh_proof** out) {
   if (!traces) return MH_ERR_INVALID;
+  if (!traces[BYTE_PAIR_LUT] || traces[BYTE_PAIR_LUT]->log_n != LOG_BPL_HEIGHT) {  // as mh_prove_precompile
+    if (ctx) ctx->err = "mh_prove_precompile: the BytePairLut trace (index 3) has 2^16 rows";
+    return MH_ERR_INVALID;
+  }
   return prove_common(ctx, s, hash_fn, nullptr, nullptr, traces, public_root, out);
+}
+
+// The setup commitment of the byte-pair table under `hash_fn`, derived on the HOST (mh_commit_host: no context, no GPU) from the table
+// itself -- what the reference's verifier does (session/preprocessed_cache.rs) -- once per hash function and process, then kept.
+int mh_precompile_setup_root(int hash_fn, uint64_t root[4]) {
+  if (!root || !lmcs_ok(hash_fn)) return MH_ERR_INVALID;
+  static std::mutex lock[N_LMCS];
+  static bool have[N_LMCS] = {};
+  static u64 kept[N_LMCS][4];
+  std::lock_guard<std::mutex> hold(lock[hash_fn]);  // a second caller waits for the first one's result instead of computing it again
+  if (!have[hash_fn]) {
+    mh_pcs_params prm;
+    mh_precompile_pcs_params(&prm);
+    const std::vector<u64> tab = byte_pair_table();
+    const uint64_t* mats[1] = {tab.data()};
+    const uint8_t lh[1] = {LOG_BPL_HEIGHT};
+    const size_t w[1] = {4};
+    const int rc = mh_commit_host(hash_fn, 1, mats, lh, w, prm.log_blowup, kept[hash_fn], nullptr, 0);
+    if (rc != MH_OK) return rc;  // out of memory: nothing is kept, the next call tries again
+    have[hash_fn] = true;
+  }
+  memcpy(root, kept[hash_fn], 32);
+  return MH_OK;
 }
 
 int mh_verify_precompile(int hash_fn, const uint64_t preprocessed_root[4], const uint64_t public_root[4], const uint8_t* proof_bytes,
@@ -226,7 +264,21 @@ int mh_verify_precompile(int hash_fn, const uint64_t preprocessed_root[4], const
     if (err && err_cap) snprintf(err, err_cap, "%s", msg);
     return MH_ERR_INVALID;
   };
-  if (!proof_bytes || !digest || !preprocessed_root || !public_root || !lmcs_ok(hash_fn)) return fail("null or malformed argument");
+  if (!proof_bytes || !digest || !public_root || !lmcs_ok(hash_fn)) return fail("null or malformed argument");
+  // the setup commitment is part of the STATEMENT: the verifier derives it from the table it knows; a root handed in is only ever
+  // compared with that one, before a byte of the proof is read
+  u64 setup[4];
+  if (const int rc = mh_precompile_setup_root(hash_fn, setup)) {
+    (void)fail("the byte-pair table's setup commitment could not be derived (out of host memory)");
+    return rc;
+  }
+  if (preprocessed_root) {
+    const bool felts = hash_fn != MH_LMCS_BLAKE3 && hash_fn != MH_LMCS_KECCAK;  // a byte digest's words are not field elements
+    for (int i = 0; i < 4; i++)
+      if ((felts ? gl_canon(preprocessed_root[i]) : preprocessed_root[i]) != setup[i])
+        return fail("preprocessed_root is not the byte-pair table's setup commitment under this hash function");
+  }
+  preprocessed_root = setup;
   mh_pcs_params prm;
   mh_precompile_pcs_params(&prm);
   u64 pre[MH_PRECOMPILE_PRE_OBSERVE_FELTS], state[12] = {0};

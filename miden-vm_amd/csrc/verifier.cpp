@@ -12,15 +12,11 @@
 #include "challenger.hpp"
 #include "gl.cuh"
 #include "kernels.hpp"
+#include "lmcs_host.hpp"
 #include <algorithm>
 #include <cstring>
 #include <numeric>
 #include <string>
-
-// p2_host_simd.cpp: eight Poseidon2 permutations per AVX-512 call (host only; the tree tops of the prover use them too)
-bool p2_host_simd_available();
-void p2_host_compress8(const uint64_t* pairs, int n, uint64_t* out);
-void p2_host_permute8(uint64_t* states);
 
 namespace {
 
@@ -82,61 +78,14 @@ size_t align8(size_t w) {
   return (w + a - 1) / a * a;
 }
 
-// Overwrite-mode sponge over whole (already aligned / short) rows: crates/stateful-hasher/src/field_sponge.rs:41-59.
-void absorb(u64 st[12], const u64* v, size_t n) {
-  for (size_t off = 0; off < n; off += 8) {
-    const size_t k = std::min<size_t>(8, n - off);
-    for (size_t i = 0; i < k; i++) st[i] = v[off + i];
-    for (size_t i = k; i < 8; i++) st[i] = 0;
-    alg_permute(t_hash, st);
-  }
-}
-Digest4 compress2(const Digest4& l, const Digest4& r) {
-  if (t_hash == MH_LMCS_BLAKE3) {  // blake3(left || right)
-    uint8_t msg[64], d[32];
-    memcpy(msg, l.data(), 32);
-    memcpy(msg + 32, r.data(), 32);
-    b3::hash_bytes(msg, 64, d);
-    Digest4 o;
-    memcpy(o.data(), d, 32);
-    return o;
-  }
-  if (t_hash == MH_LMCS_KECCAK) {
-    Digest4 o;
-    kk::compress_pair(l.data(), r.data(), o.data());
-    return o;
-  }
-  u64 st[12] = {l[0], l[1], l[2], l[3], r[0], r[1], r[2], r[3], 0, 0, 0, 0};
-  alg_permute(t_hash, st);
-  return Digest4{st[0], st[1], st[2], st[3]};
-}
+// The hashers themselves are lmcs_host.hpp (shared with the host commitment, commit_host.cpp); here they take the call's configuration.
+Digest4 compress2(const Digest4& l, const Digest4& r) { return lmcs_host::compress2(t_hash, l, r); }
 // leaf digest of one opened index: the rows of the tree's matrices, each already of its aligned width
 Digest4 leaf_digest(const u64* row, const std::vector<size_t>& widths) {
+  u64 st[lmcs_host::MAX_STATE_WORDS] = {0};
   size_t off = 0;
-  if (t_hash == MH_LMCS_BLAKE3) {  // chaining hasher: state := blake3(state || row bytes), zero state first (chaining.rs:32-50)
-    Digest4 st{0, 0, 0, 0};
-    for (size_t w : widths) {
-      std::vector<uint8_t> msg(32 + 8 * w);
-      memcpy(msg.data(), st.data(), 32);
-      if (w) memcpy(msg.data() + 32, row + off, 8 * w);
-      uint8_t d[32];
-      b3::hash_bytes(msg.data(), msg.size(), d);
-      memcpy(st.data(), d, 32);
-      off += w;
-    }
-    return st;
-  }
-  if (t_hash == MH_LMCS_KECCAK) {
-    u64 st[25] = {0};
-    for (size_t w : widths) {
-      kk::lmcs_absorb(st, row + off, w);
-      off += w;
-    }
-    return Digest4{st[0], st[1], st[2], st[3]};
-  }
-  u64 st[12] = {0};
   for (size_t w : widths) {
-    absorb(st, row + off, w);
+    lmcs_host::leaf_absorb(t_hash, st, row + off, w);
     off += w;
   }
   return Digest4{st[0], st[1], st[2], st[3]};
@@ -145,7 +94,7 @@ Digest4 leaf_digest(const u64* row, const std::vector<size_t>& widths) {
 // The Poseidon2 configuration, eight hashes per AVX-512 permutation (p2_host_simd.cpp: the tree tops of the prover use the same code): the leaves of a
 // batch opening absorb rows of the same shape in lockstep, the compressions of one tree level are independent of each other.  A Miden proof under
 // Poseidon2 verifies in ~1 ms instead of 4.6 (tools/bench_verify.py); the other configurations and CPUs without AVX-512 take the scalar functions above.
-bool simd_hashing() { return t_hash == MH_LMCS_POSEIDON2 && p2_host_simd_available(); }
+bool simd_hashing() { return lmcs_host::simd(t_hash); }
 
 std::vector<Digest4> leaf_digests(const std::vector<std::vector<u64>>& rows, const std::vector<size_t>& widths) {
   std::vector<Digest4> out(rows.size());
@@ -155,20 +104,15 @@ std::vector<Digest4> leaf_digests(const std::vector<std::vector<u64>>& rows, con
   }
   for (size_t q0 = 0; q0 < rows.size(); q0 += 8) {
     const size_t n = std::min<size_t>(8, rows.size() - q0);
-    u64 st[8][12] = {{0}};
+    u64 st[8 * 12] = {0};
+    const u64* at[8];
     size_t off = 0;
-    for (size_t w : widths) {  // absorb(), eight leaves abreast
-      for (size_t o = 0; o < w; o += 8) {
-        const size_t k = std::min<size_t>(8, w - o);
-        for (size_t j = 0; j < n; j++) {
-          for (size_t i = 0; i < k; i++) st[j][i] = gl_canon(rows[q0 + j][off + o + i]);
-          for (size_t i = k; i < 8; i++) st[j][i] = 0;
-        }
-        p2_host_permute8(&st[0][0]);
-      }
+    for (size_t w : widths) {  // leaf_absorb, eight leaves abreast
+      for (size_t j = 0; j < n; j++) at[j] = rows[q0 + j].data() + off;
+      lmcs_host::leaf_absorb8(st, at, n, w);
       off += w;
     }
-    for (size_t j = 0; j < n; j++) out[q0 + j] = Digest4{st[j][0], st[j][1], st[j][2], st[j][3]};
+    for (size_t j = 0; j < n; j++) out[q0 + j] = Digest4{st[12 * j], st[12 * j + 1], st[12 * j + 2], st[12 * j + 3]};
   }
   return out;
 }
@@ -180,15 +124,15 @@ std::vector<Digest4> compress_many(const std::vector<std::pair<Digest4, Digest4>
     return out;
   }
   for (size_t i0 = 0; i0 < pairs.size(); i0 += 8) {
-    const int n = (int)std::min<size_t>(8, pairs.size() - i0);
+    const size_t n = std::min<size_t>(8, pairs.size() - i0);
     u64 in[64], o[32];
-    for (int j = 0; j < n; j++)
+    for (size_t j = 0; j < n; j++)
       for (int k = 0; k < 4; k++) {
-        in[8 * j + k] = gl_canon(pairs[i0 + j].first[k]);
-        in[8 * j + 4 + k] = gl_canon(pairs[i0 + j].second[k]);
+        in[8 * j + k] = pairs[i0 + j].first[k];
+        in[8 * j + 4 + k] = pairs[i0 + j].second[k];
       }
-    p2_host_compress8(in, n, o);
-    for (int j = 0; j < n; j++) out[i0 + j] = Digest4{o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]};
+    lmcs_host::compress8(in, n, o);
+    for (size_t j = 0; j < n; j++) out[i0 + j] = Digest4{o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]};
   }
   return out;
 }
