@@ -16,7 +16,9 @@
 //     on it as radix-16 rounds in registers; strided passes move >=128-byte contiguous segments.
 // Roofline: algorithmic bytes per column = (1 + B) * N * 8 (read trace once, write LDE once), two
 // passes move (4 + 4B) * N * 8; measured, the passes are VALU-issue bound (no 64-bit multiplier on
-// CDNA4: ~23 VALU instructions per element-stage), see DESIGN.md section 3.
+// CDNA4): a radix-16 round costs ~13 VALU instructions per element for its table twiddle and ~25 for its four
+// butterfly stages (wide values, one reduction per output and round: NTT_ASM_BFLY == 2 below; the per-butterfly
+// reductions of form 1 cost ~34), see DESIGN.md sections 3 and 8.
 #include "ctx.hpp"
 #include "gl.cuh"
 #include "kernels.hpp"
@@ -215,7 +217,7 @@ __device__ __forceinline__ void ntt_bfly_dif(u64& a, u64& b, int E) {
   a = s;
   b = E % 96 ? ntt_mul_pow2(d, E % 96) : d;
 }
-// ---- the forward (DIT) register DFT with hand-placed carry chains (NTT_ASM_BFLY, default 1) ----------------------------------
+// ---- the forward (DIT) register DFT with hand-placed carry chains (NTT_ASM_BFLY == 1) ------------------------------------------
 // The C butterflies above cost hipcc ~14 VALU instructions without a shift and ~30 with one (every carry a v_cmp_lt_u64 +
 // v_cndmask pair, every 32 -> 64-bit composition a v_mov / v_or); a radix-16 round spent 870 of its ~1130 VALU instructions
 // there.  Here a stage's 2^(G-1) butterflies run as ONE stage-interleaved sequence of single-instruction asm statements, the way
@@ -225,7 +227,7 @@ __device__ __forceinline__ void ntt_bfly_dif(u64& a, u64& b, int E) {
 //   every butterfly:    t = canonical(r or b) (4), a + t (4), a - t (4); E >= 96 (2^96 = -1) swaps the two outputs.
 // 12 VALU for a plain butterfly, 21-22 for a shifted one: ~545 per radix-16 round instead of 870.
 #ifndef NTT_ASM_BFLY
-#define NTT_ASM_BFLY 1
+#define NTT_ASM_BFLY 2  // 0 = the C butterflies, 1 = this form (forward rounds of 8 / 16 points), 2 = the wide form below (default)
 #endif
 #define NTT_A asm volatile
 // carry-outs nobody reads rotate through fixed scratch SGPR pairs (hipcc separates asm statements that share a register by s_nop)
@@ -423,10 +425,175 @@ __device__ __forceinline__ void ntt_fwd_dft_asm(u64 (&x)[1 << G]) {
   }
 }
 
+// ---- the register DFT on WIDE values, one reduction per output and round (NTT_ASM_BFLY == 2), both directions --------------------
+// Inside a round a value is a signed 96-bit integer w0 + w1 2^32 + w2 2^64 (w2 signed) congruent to the field element:
+//   butterfly: one 3-instruction add chain and one 3-instruction subtract chain -- no canonical operand, no select, no flag arithmetic;
+//   b * 2^S, S = 32 q + r:  y = b << r (3 instructions: y2 = the signed top word stays small, tools/ntt_wide_bounds.py), then a word move
+//     with 2^64 = 2^32 - 1 and 2^96 = -1:  q = 0: y;   q = 1: (y1 eps + y0 2^32) - y2;   q = 2: y0 eps - (y1 + y2 2^32)
+//     (one v_mad_u64_u32 whose carry is the new top word, one subtract chain); S >= 96 trades the two outputs;
+//   fold: lo + w2 eps for a NON-NEGATIVE value: v_mad_u64_u32, and its carry worth eps once more (select + v_mad_u64_u32).
+// Non-negative by construction: element 0 of the round carries Z = 2^30 p; it reaches every output with coefficient 1 and never passes
+// through a shift.  The few operands whose shift would leave 96 bits are folded first (NTT_WIDE_FOLD_*: byte m = stage m, bit j = twiddle
+// index e & (2^m - 1)), with Z added.  Every bound is computed on exact integers by tools/ntt_wide_bounds.py (tests/test_ntt_wide_bounds.py).
+#define NTT_WIDE_FOLD_FWD 0x22000000u
+#define NTT_WIDE_FOLD_INV 0x000C0200u
+#if P2F_ASM && NTT_ASM_BFLY == 2
+struct NttW {
+  u32 w0, w1, w2;
+};
+__device__ __forceinline__ NttW ntt_w_from(u64 x) { return NttW{lo32(x), hi32(x), 0u}; }
+// + Z = 2^30 p = 2^94 - 2^62 + 2^30 = (0x40000000, 0xC0000000, 0x3FFFFFFF)
+__device__ __forceinline__ NttW ntt_w_bias(NttW a) {
+  const u64 zlo = 0xC000000040000000ULL, lo = (((u64)a.w1 << 32) | a.w0) + zlo;
+  return NttW{lo32(lo), hi32(lo), a.w2 + 0x3FFFFFFFu + (lo < zlo ? 1u : 0u)};
+}
+// a - b, one chain on its own (the operands of the shifts); carry consumers bring their own wait states (as p2f_mul_nv)
+__device__ __forceinline__ NttW ntt_w_sub1(NttW a, NttW b) {
+  NttW d;
+  u64 b0, b1, b2;
+  asm("v_sub_co_u32_e64 %0, %1, %2, %3" : "=v"(d.w0), "=s"(b0) : "v"(a.w0), "v"(b.w0));
+  asm("s_nop 1\n\tv_subb_co_u32_e64 %0, %1, %2, %3, %4" : "=v"(d.w1), "=s"(b1) : "v"(a.w1), "v"(b.w1), "s"(b0));
+  asm("s_nop 1\n\tv_subb_co_u32_e64 %0, %1, %2, %3, %4" : "=v"(d.w2), "=s"(b2) : "v"(a.w2), "v"(b.w2), "s"(b1));
+  return d;
+}
+// a non-negative wide value -> a representative below 2^64 (one value on its own: the operands folded before a shift)
+__device__ __forceinline__ u64 ntt_w_fold1(NttW v) {
+  u64 t, c, r, d0;
+  u32 m;
+  const u64 lo = ((u64)v.w1 << 32) | v.w0;
+  asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(t), "=s"(c) : "v"(v.w2), "v"(lo));
+  asm("s_nop 1\n\tv_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(m) : "s"(c));  // the carry: 2^64 = eps; t + eps cannot carry again
+  asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(r), "=s"(d0) : "v"(m), "v"(t));
+  return r;
+}
+// the same for N values, stage-interleaved: every carry has its wait states from the other chains
+template <int N>
+__device__ __forceinline__ void ntt_w_foldN(u64 (&r)[N], const u32 (&w0)[N], const u32 (&w1)[N], const u32 (&w2)[N]) {
+  u64 t[N], c[N];
+  u32 m[N];
+#pragma unroll
+  for (int i = 0; i < N; i++) NTT_A("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(t[i]), "=s"(c[i]) : "v"(w2[i]), "v"(((u64)w1[i] << 32) | w0[i]));
+  if constexpr (N < 3) NTT_A("s_nop 1");
+#pragma unroll
+  for (int i = 0; i < N; i++) NTT_A("v_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(m[i]) : "s"(c[i]));
+#pragma unroll
+  for (int i = 0; i < N; i++) NTT_DEAD(i, "v_mad_u64_u32 %0, ", ", %1, 1, %2", "=v"(r[i]) : "v"(m[i]), "v"(t[i]));
+}
+// (s[i], d[i]) = (a[i] + t[i], p[i] - q[i]) on wide values, N butterflies as one stage-interleaved sequence: 6 instructions each
+template <int N>
+__device__ __forceinline__ void ntt_w_bflyN(NttW (&s)[N], NttW (&d)[N], const NttW (&a)[N], const NttW (&t)[N], const NttW (&p)[N],
+                                            const NttW (&q)[N]) {
+  u64 ca[N], cb[N], ba[N], bb[N];
+#pragma unroll
+  for (int i = 0; i < N; i++) NTT_A("v_add_co_u32_e64 %0, %1, %2, %3" : "=v"(s[i].w0), "=s"(ca[i]) : "v"(a[i].w0), "v"(t[i].w0));
+#pragma unroll
+  for (int i = 0; i < N; i++) NTT_A("v_sub_co_u32_e64 %0, %1, %2, %3" : "=v"(d[i].w0), "=s"(ba[i]) : "v"(p[i].w0), "v"(q[i].w0));
+  if constexpr (N == 1) NTT_A("s_nop 0");
+#pragma unroll
+  for (int i = 0; i < N; i++) NTT_A("v_addc_co_u32_e64 %0, %1, %2, %3, %4" : "=v"(s[i].w1), "=s"(cb[i]) : "v"(a[i].w1), "v"(t[i].w1), "s"(ca[i]));
+#pragma unroll
+  for (int i = 0; i < N; i++) NTT_A("v_subb_co_u32_e64 %0, %1, %2, %3, %4" : "=v"(d[i].w1), "=s"(bb[i]) : "v"(p[i].w1), "v"(q[i].w1), "s"(ba[i]));
+  if constexpr (N == 1) NTT_A("s_nop 0");
+#pragma unroll
+  for (int i = 0; i < N; i++) NTT_DEAD(i, "v_addc_co_u32_e64 %0, ", ", %1, %2, %3", "=v"(s[i].w2) : "v"(a[i].w2), "v"(t[i].w2), "s"(cb[i]));
+#pragma unroll
+  for (int i = 0; i < N; i++) NTT_DEAD(i + 2, "v_subb_co_u32_e64 %0, ", ", %1, %2, %3", "=v"(d[i].w2) : "v"(p[i].w2), "v"(q[i].w2), "s"(bb[i]));
+}
+// b * 2^S (mod p), 0 < S < 96, S a constant once the round is unrolled
+__device__ __forceinline__ NttW ntt_w_shl(NttW b, int S) {
+  const int q = S >> 5, r = S & 31;
+  const u32 y0 = r ? (b.w0 << r) : b.w0;
+  const u32 y1 = r ? __builtin_amdgcn_alignbit(b.w1, b.w0, 32 - r) : b.w1;
+  const u32 y2 = r ? __builtin_amdgcn_alignbit(b.w2, b.w1, 32 - r) : b.w2;
+  if (q == 0) return NttW{y0, y1, y2};
+  const u32 ys = (u32)((int)y2 >> 31);  // the sign of y2 as a word
+  if (q == 1) {
+    u64 t, c, d0;
+    u32 h;
+    const u64 a0 = (u64)y0 << 32;
+    asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(t), "=s"(c) : "v"(y1), "v"(a0));
+    asm("s_nop 1\n\tv_addc_co_u32_e64 %0, %1, 0, 0, %2" : "=v"(h), "=s"(d0) : "s"(c));
+    return ntt_w_sub1(NttW{lo32(t), hi32(t), h}, NttW{y2, ys, ys});
+  }
+  const u64 pe = (u64)y0 * 0xFFFFFFFFu;
+  return ntt_w_sub1(NttW{lo32(pe), hi32(pe), 0u}, NttW{y1, y2, ys});
+}
+// butterflies K0 .. K0 + N - 1 of stage M
+template <int G, bool INV, int M, int K0, int N>
+__device__ __forceinline__ void ntt_w_stage_part(u32 (&v0)[1 << G], u32 (&v1)[1 << G], u32 (&v2)[1 << G]) {
+  constexpr int W16 = INV ? 36 : 156;
+  constexpr u32 FOLD = INV ? NTT_WIDE_FOLD_INV : NTT_WIDE_FOLD_FWD;
+  NttW a[N], t[N], p[N], q[N], s[N], d[N];
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    const int e = ntt_bfly_lo(M, K0 + i), f = e | (1 << M), j = e & ((1 << M) - 1);
+    const int E = (W16 * (8 >> M) * j) % 192, S = E % 96;
+    const bool pre = (FOLD >> (8 * M + j)) & 1u;
+    a[i] = NttW{v0[e], v1[e], v2[e]};
+    t[i] = NttW{v0[f], v1[f], v2[f]};
+    if (!INV) {  // (a, b) <- (a + 2^E b, a - 2^E b)
+      if (S) t[i] = ntt_w_shl(pre ? ntt_w_from(ntt_w_fold1(ntt_w_bias(t[i]))) : t[i], S);
+      p[i] = a[i];
+      q[i] = t[i];
+    } else {  // (a, b) <- (a + b, 2^E (a - b)); 2^96 = -1 turns the difference round
+      p[i] = E >= 96 ? t[i] : a[i];
+      q[i] = E >= 96 ? a[i] : t[i];
+    }
+  }
+  ntt_w_bflyN<N>(s, d, a, t, p, q);
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    const int e = ntt_bfly_lo(M, K0 + i), f = e | (1 << M), j = e & ((1 << M) - 1);
+    const int E = (W16 * (8 >> M) * j) % 192, S = E % 96;
+    const bool pre = (FOLD >> (8 * M + j)) & 1u;
+    NttW lo = s[i], hi = d[i];
+    if (!INV) {
+      if (E >= 96) { lo = d[i]; hi = s[i]; }
+    } else if (S) {
+      hi = ntt_w_shl(pre ? ntt_w_from(ntt_w_fold1(ntt_w_bias(hi))) : hi, S);
+    }
+    v0[e] = lo.w0; v1[e] = lo.w1; v2[e] = lo.w2;
+    v0[f] = hi.w0; v1[f] = hi.w1; v2[f] = hi.w2;
+  }
+}
+template <int G, bool INV, int I = 0>
+__device__ __forceinline__ void ntt_w_stages(u32 (&v0)[1 << G], u32 (&v1)[1 << G], u32 (&v2)[1 << G]) {
+  if constexpr (I < G) {
+    constexpr int M = INV ? G - 1 - I : I, H = 1 << (G - 1), N = H < NTT_ILV ? H : NTT_ILV;
+    ntt_w_stage_part<G, INV, M, 0, N>(v0, v1, v2);
+    if constexpr (H > N) ntt_w_stage_part<G, INV, M, N, H - N>(v0, v1, v2);
+    ntt_w_stages<G, INV, I + 1>(v0, v1, v2);
+  }
+}
+template <int G, bool INV>
+__device__ __forceinline__ void ntt_dft_wide(u64 (&x)[1 << G]) {
+  u32 v0[1 << G], v1[1 << G], v2[1 << G];  // three word arrays, not an array of NttW: every word a register of its own
+#pragma unroll
+  for (int e = 0; e < (1 << G); e++) { v0[e] = lo32(x[e]); v1[e] = hi32(x[e]); v2[e] = 0u; }
+  const NttW z = ntt_w_bias(NttW{v0[0], v1[0], 0u});
+  v0[0] = z.w0; v1[0] = z.w1; v2[0] = z.w2;
+  ntt_w_stages<G, INV>(v0, v1, v2);
+  constexpr int NF = (1 << G) < NTT_ILV ? (1 << G) : NTT_ILV;
+#pragma unroll
+  for (int c = 0; c < (1 << G); c += NF) {
+    u64 r[NF];
+    u32 f0[NF], f1[NF], f2[NF];
+#pragma unroll
+    for (int i = 0; i < NF; i++) { f0[i] = v0[c + i]; f1[i] = v1[c + i]; f2[i] = v2[c + i]; }
+    ntt_w_foldN<NF>(r, f0, f1, f2);
+#pragma unroll
+    for (int i = 0; i < NF; i++) x[c + i] = r[i];
+  }
+}
+#endif
+
 // 2^G-point DFT on registers; position bit m is stage m.  DIT: bit-reversed in, natural out; DIF: the transpose.
 template <int G, bool INV>
 __device__ __forceinline__ void ntt_dft_regs(u64 (&x)[1 << G], bool dif) {
-#if P2F_ASM && NTT_ASM_BFLY
+#if P2F_ASM && NTT_ASM_BFLY == 2
+  ntt_dft_wide<G, INV>(x);
+  return;
+#elif P2F_ASM && NTT_ASM_BFLY
   if constexpr (!INV && G >= 3) {  // the forward passes (8/9 of an LDE); 4 or 8 butterflies per stage keep every carry 2 wait states away
     ntt_fwd_dft_asm<G>(x);
     return;
