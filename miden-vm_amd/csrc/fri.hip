@@ -56,7 +56,11 @@ __device__ __forceinline__ void fri_leaf_hash_body(const u64* __restrict__ ev, i
       st[2 * k] = (p0 + k < arity) ? v.c0 : 0;
       st[2 * k + 1] = (p0 + k < arity) ? v.c1 : 0;
     }
-    p2f_permute(st);
+    // one body, the tail by a wave-uniform branch (as in k_leaf_absorb): the capacity between chunks, the digest after the last
+    p2f_body(st);
+    if (p0 + 4 < arity) p2f_tail<P2F_CAPACITY>(st);
+    else if (SALT) p2f_tail<P2F_ALL>(st);
+    else p2f_tail<P2F_DIGEST>(st);
   }
   if constexpr (SALT) salt_absorb_p2(st, *sa, salt_phys_row(j, r0, cbits, log_q + cbits));
   ulonglong2* o = reinterpret_cast<ulonglong2*>(digests + 4 * s);

@@ -118,6 +118,14 @@ __device__ __forceinline__ void leaf_absorb_body(const LeafArgs& a, const SaltAr
     for (int i = 0; i < 12; i++) s[i] = 0;
   }
   const size_t col_stride = leaves;  // B * N
+  // Every permutation but the last is an intermediate sponge step: the next chunk overwrites the rate, only the capacity is carried
+  // (p2f_tail<P2F_CAPACITY>).  The last one feeds the digest, the carried-state buffer (canonical, all twelve) or the salt's absorb.
+  // The permutation's body stands ONCE in the loop and the wave-uniform branch chooses only the tail: two copies of the body would
+  // not fit the instruction cache.
+  int last_mi = -1;  // the last matrix that has a column
+#pragma unroll 1
+  for (int mi = 0; mi < a.n_mats; mi++)
+    if (a.m[mi].width) last_mi = mi;
 #pragma unroll 1
   for (int mi = 0; mi < a.n_mats; mi++) {
     const u64* base = a.m[mi].data + q;
@@ -126,7 +134,10 @@ __device__ __forceinline__ void leaf_absorb_body(const LeafArgs& a, const SaltAr
     for (u32 c0 = 0; c0 < w; c0 += 8) {
 #pragma unroll
       for (int k = 0; k < 8; k++) s[k] = (c0 + k < w) ? base[(size_t)(c0 + k) * col_stride] : 0;
-      p2f_permute(s);
+      p2f_body(s);
+      if (!(mi == last_mi && c0 + 8 >= w)) p2f_tail<P2F_CAPACITY>(s);
+      else if (SALT || !a.digest_out) p2f_tail<P2F_ALL>(s);
+      else p2f_tail<P2F_DIGEST>(s);
     }
   }
   if constexpr (SALT) salt_absorb_p2(s, *sa, salt_phys_row(j, r, a.log_blowup, a.log_n + a.log_blowup));
@@ -428,7 +439,8 @@ __global__ __launch_bounds__(256) void k_compress(const u64* __restrict__ in, u6
   const ulonglong2* pr = reinterpret_cast<const ulonglong2*>(in + 4 * rgt);
   ulonglong2 l0 = pl[0], l1 = pl[1], r0 = pr[0], r1 = pr[1];
   u64 s[12] = {l0.x, l0.y, l1.x, l1.y, r0.x, r0.y, r1.x, r1.y, 0, 0, 0, 0};
-  p2f_permute(s);
+  p2f_body(s);
+  p2f_tail<P2F_DIGEST>(s);  // only the digest is stored
   ulonglong2* o = reinterpret_cast<ulonglong2*>(out + 4 * q);
   o[0] = make_ulonglong2(s[0], s[1]);
   o[1] = make_ulonglong2(s[2], s[3]);

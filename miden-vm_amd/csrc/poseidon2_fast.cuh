@@ -19,7 +19,9 @@
 //   * the diagonal pairs (+k, -k) -- elements (3,6), (4,7), (5,8), (9,10) -- are carried as h = (x_i + x_j)/2, whose
 //     two-step recurrence h(r+1) = k^2 h(r-1) + 8*sum is ONE shift-add per part and round (no 64-bit subtraction, which is
 //     two instructions plus the shift), and the sum reads one value per pair; tests/test_p2_fast_schedule.py checks the algebra
-//     on exact integers, tools/p2_pair_bounds.py the magnitudes.  10 953 -> 10 120 VALU instructions per permutation.
+//     on exact integers, tools/p2_pair_bounds.py the magnitudes.  10 953 -> 10 120 VALU instructions per permutation;
+//   * the round constants of the external rounds are addends of products that are issued anyway (P2F_RC_ADDEND, p2f_body), and
+//     a sponge step or a compression finishes only the outputs it uses (P2F_TAILS, p2f_tail<OUT>).
 #pragma once
 #include "poseidon2.cuh"
 
@@ -32,6 +34,16 @@ namespace p2c {
 #endif
 #ifndef P2F_GROUP
 #define P2F_GROUP 4  // S-boxes of an external round interleaved per asm block
+#endif
+#ifndef P2F_RC_ADDEND
+#define P2F_RC_ADDEND 1  // 1: round constants of the external rounds ride as addends of products (p2f_mulN<.., KA>); 0: added after the layers
+#endif
+#if !P2F_ASM
+#undef P2F_RC_ADDEND
+#define P2F_RC_ADDEND 0  // the addends live in the asm form of the product
+#endif
+#ifndef P2F_TAILS
+#define P2F_TAILS 1  // 1: the sponges and the compression finish only the outputs they use (p2f_tail<OUT>); 0: all twelve, canonical
 #endif
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -66,6 +78,11 @@ __device__ __forceinline__ u32 hi32(u64 x) { return (u32)(x >> 32); }
 //        p00 = a0*b0;  m = a0*b1;  m += a1*b0 (carry cm);  w1 = p00.hi + m.lo (k1);  acc.lo = m.hi + k1 (k2);
 //        acc.hi = cm|k2;  hi = a1*b1 + acc;  lo = {p00.lo, w1}
 //        t = hi.lo*(2^32-1) + lo (c1);   r = t - hi.hi + (c1 - borrow)*(2^32-1)   [2^64 = 2^32-1, 2^96 = -1 mod p]
+//    KA: a*b + K for a wave-uniform K = Kl + Kh 2^32 < 2^64 at no cost: the first two mads accumulate Kl and Kh (an SGPR pair each,
+//    {Kl, 0} and {Kh, 0}) where the plain product accumulates the literal 0.  a0*b0 + Kl and a0*b1 + Kh stay below 2^64
+//    ((2^32-1)^2 + 2^32 - 1 = 2^64 - 2^32); with Kh included a carried m leaves m.hi <= 2^32 - 3, so cm and k2 still exclude each
+//    other; a*b + K <= 2^128 - 2^64, and everything behind the two mads is the same code reducing that 128-bit value.  Not with BS:
+//    a gfx9 VOP3 instruction reads one scalar operand, and the BS form spends it on b.
 //    gfx950 needs 2 wait states between a VALU that writes an SGPR and a VALU that reads it; the statements are
 //    `asm volatile` (kept in program order), N independent products are interleaved stage by stage so that for
 //    N >= 3 the distance is there by construction, and N = 1, 2 insert the missing s_nop themselves.
@@ -116,20 +133,26 @@ __device__ __forceinline__ u64 p2f_mul_c(u64 a, u64 b) {
 // the same with the second factor in scalar registers (a wave-uniform constant: no v_mov of its halves into VGPRs)
 #define P2F_MAD0S(i, D, X, Y) P2F_SCR(i, "v_mad_u64_u32 %0, ", ", %1, %2, 0", "=v"(D) : "v"(X), "s"(Y))
 #define P2F_MADAS(i, D, X, Y, ACC) P2F_SCR(i, "v_mad_u64_u32 %0, ", ", %1, %2, %3", "=v"(D) : "v"(X), "s"(Y), "v"(ACC))
+// the addend in scalar registers (KA: one 32-bit half of a wave-uniform constant, zero-extended to an SGPR pair)
+#define P2F_MADK(i, D, X, Y, K) P2F_SCR(i, "v_mad_u64_u32 %0, ", ", %1, %2, %3", "=v"(D) : "v"(X), "v"(Y), "s"(K))
 // BS: every b[i] is wave-uniform (a table constant); it is read from SGPRs
-template <int N, bool BS = false>
-__device__ __forceinline__ void p2f_mulN(u64 (&r)[N], const u64 (&a)[N], const u64 (&b)[N]) {
+// KA: r[i] = a[i]*b[i] + K_i, the wave-uniform K_i pre-split as ka[2 i] = lo32(K_i), ka[2 i + 1] = hi32(K_i)
+template <int N, bool BS = false, bool KA = false>
+__device__ __forceinline__ void p2f_mulN(u64 (&r)[N], const u64 (&a)[N], const u64 (&b)[N], const unsigned long long* ka = nullptr) {
+  static_assert(!(BS && KA), "one scalar operand per VOP3 instruction: b in SGPRs and an SGPR addend exclude each other");
   u64 p00[N], m[N], hi[N], t[N];
   u64 cm[N], k1[N], k2[N], k3[N], c1[N], bb[N], bw[N], c3[N];  // SGPR pairs: lane masks of carries
   u32 w1[N], accl[N], acch[N], rl[N], rh[N];
 #pragma unroll
   for (int i = 0; i < N; i++) {
     if constexpr (BS) P2F_MAD0S(i, p00[i], lo32(a[i]), lo32(b[i]));
+    else if constexpr (KA) P2F_MADK(i, p00[i], lo32(a[i]), lo32(b[i]), ka[2 * i]);
     else P2F_MAD0(i, p00[i], lo32(a[i]), lo32(b[i]));
   }
 #pragma unroll
   for (int i = 0; i < N; i++) {
     if constexpr (BS) P2F_MAD0S(i, m[i], lo32(a[i]), hi32(b[i]));
+    else if constexpr (KA) P2F_MADK(i, m[i], lo32(a[i]), hi32(b[i]), ka[2 * i + 1]);
     else P2F_MAD0(i, m[i], lo32(a[i]), hi32(b[i]));
   }
 #pragma unroll
@@ -143,7 +166,7 @@ __device__ __forceinline__ void p2f_mulN(u64 (&r)[N], const u64 (&a)[N], const u
 #pragma unroll
   for (int i = 0; i < N; i++) P2F_A("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(accl[i]), "=s"(k2[i]) : "v"(hi32(m[i])), "s"(k1[i]));
 #pragma unroll
-  for (int i = 0; i < N; i++)  // cm and k2 exclude each other (a carried m leaves m.hi <= 2^32 - 5)
+  for (int i = 0; i < N; i++)  // cm and k2 exclude each other (a carried m leaves m.hi <= 2^32 - 5; KA: <= 2^32 - 3)
     k3[i] = cm[i] | k2[i];  // scalar unit
 #pragma unroll
   for (int i = 0; i < N; i++) {
@@ -188,6 +211,7 @@ __device__ __forceinline__ void p2f_mulN(u64 (&r)[N], const u64 (&a)[N], const u
 #undef P2F_MADA
 #undef P2F_MAD0S
 #undef P2F_MADAS
+#undef P2F_MADK
 #undef P2F_CARRY_IN
 // The same 13-instruction product with NON-volatile statements, each carry consumer carrying its own 2 wait states: for
 // code whose schedule must stay free (loads hoisted above the products, independent products interleaved by the compiler:
@@ -250,8 +274,26 @@ __device__ __forceinline__ u64 p2f_sbox(u64 x) {
   return p2f_mul(x3, x4);
 #endif
 }
+// The addends of one group of products, W words of a 64-byte aligned table (p2c::P2F_EXT_K).  Eight words -- four constants -- are ONE
+// scalar load of 16 dwords: left to itself the compiler loads every word on its own, between the asm statements, with the address
+// arithmetic repeated (4 SALU instructions and a wait per word).
+template <int W>
+__device__ __forceinline__ void p2f_load_k(unsigned long long (&d)[W], const unsigned long long* k) {
+  if constexpr (W == 8) {
+    typedef unsigned long long k8 __attribute__((ext_vector_type(8)));
+    const k8 v = *reinterpret_cast<const k8*>(k);
+#pragma unroll
+    for (int i = 0; i < 8; i++) d[i] = v[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < W; i++) d[i] = k[i];
+  }
+}
 // S-box layer of an external round: the 12 S-boxes are independent; P2F_GROUP of them run interleaved.
-__device__ __forceinline__ void p2f_sbox12(u64 s[12]) {
+// KA: s[i] = s[i]^7 + k_i, the addends of the last product (x^3 * x^4), k pre-split as p2f_mulN takes it.  A template flag: as a
+// run-time test of the pointer the product would be emitted twice behind a branch.
+template <bool KA = false>
+__device__ __forceinline__ void p2f_sbox12(u64 s[12], const unsigned long long* k = nullptr) {
 #if P2F_ASM
 #pragma unroll
   for (int g = 0; g < 12; g += P2F_GROUP) {
@@ -261,11 +303,18 @@ __device__ __forceinline__ void p2f_sbox12(u64 s[12]) {
     p2f_mulN<P2F_GROUP>(x2, x, x);
     p2f_mulN<P2F_GROUP>(x3, x2, x);
     p2f_mulN<P2F_GROUP>(x, x2, x2);
-    p2f_mulN<P2F_GROUP>(x2, x3, x);
+    if constexpr (KA) {
+      unsigned long long kg[2 * P2F_GROUP];
+      p2f_load_k(kg, k + 2 * g);
+      p2f_mulN<P2F_GROUP, false, true>(x2, x3, x, kg);
+    } else {
+      p2f_mulN<P2F_GROUP>(x2, x3, x);
+    }
 #pragma unroll
     for (int i = 0; i < P2F_GROUP; i++) s[g + i] = x2[i];
   }
 #else
+  static_assert(!KA, "addends need the asm form of the product");
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = p2f_sbox(s[i]);
 #endif
@@ -353,7 +402,13 @@ __device__ __forceinline__ void p2f_pm_shl(u64 R, const u32 (&u)[3], u64& s8, u6
 
 // out = circ(2*M4, M4, M4) * s (+ rc), s given as 64-bit values; result folded back to 64 bits.
 // M4 = [[2,3,1,1],[1,2,3,1],[1,1,2,3],[3,1,1,2]]  (poseidon2/mod.rs:233-281)
-template <bool RC>
+// OUT (p2f_tail): only the elements the caller uses are finished (two 64-bit additions and a fold each); the mads are non-volatile
+// statements, so outside a rolled loop whatever feeds only an unused element goes away with it.
+enum { P2F_ALL = 0, P2F_DIGEST = 1, P2F_CAPACITY = 2 };
+__host__ __device__ constexpr bool p2f_out_has(int out, int i) {
+  return out == P2F_ALL || (out == P2F_DIGEST && i < 4) || (out == P2F_CAPACITY && i >= 8);
+}
+template <bool RC, int OUT = P2F_ALL>
 __device__ __forceinline__ void p2f_external(u64 s[12], const unsigned long long* rc) {
   u64 oL[12], oH[12];
 #pragma unroll
@@ -379,6 +434,7 @@ __device__ __forceinline__ void p2f_external(u64 s[12], const unsigned long long
     const u64 stL = oL[l] + oL[4 + l] + oL[8 + l], stH = oH[l] + oH[4 + l] + oH[8 + l];
 #pragma unroll
     for (int i = l; i < 12; i += 4) {
+      if (!p2f_out_has(OUT, i)) continue;
       u64 L = oL[i] + stL, H = oH[i] + stH;
       if (RC) {  // a template flag: as a run-time test of the pointer it became four v_cndmask per element
         L += rc[i] & 0xFFFFFFFFULL;
@@ -389,9 +445,24 @@ __device__ __forceinline__ void p2f_external(u64 s[12], const unsigned long long
   }
 }
 
-__device__ __forceinline__ void p2f_permute(u64 s[12]) {
+// The permutation in two pieces: p2f_body runs up to and including the last S-box layer, p2f_tail<OUT> is the last linear layer and
+// the canonicalisation of the outputs the caller uses.  p2f_permute = p2f_body + p2f_tail<P2F_ALL>.
+//
+// Round constants (P2F_RC_ADDEND): the constants of an external round are added BEFORE the linear layer in front of them, to the
+// S-box outputs, as k = M_E^(-1) rc (M_E (x + k) = M_E x + rc; p2c::P2F_EXT_K, one row per S-box layer) -- addends of the S-boxes'
+// last product (p2f_mulN<.., KA>), no instruction of their own.  Row 3 carries the constant of internal round 0, row 7 is zero.  The
+// constants of terminal round 0 follow the de-scale products directly and are those products' addends (p2c::P2F_TERM0_K).  Only the
+// initial layer keeps its additions: its inputs are not products.
+__device__ __forceinline__ void p2f_body(u64 s[12]) {
   // initial linear layer + round constants of external round 0
   p2f_external<true>(s, p2c::P2_ARK_EXT_INITIAL);
+#if P2F_RC_ADDEND
+#pragma unroll 1
+  for (int r = 0; r < 4; r++) {
+    p2f_sbox12<true>(s, p2c::P2F_EXT_K + 24 * r);
+    p2f_external<false>(s, nullptr);
+  }
+#else
 #pragma unroll 1
   for (int r = 0; r < 4; r++) {
     p2f_sbox12(s);
@@ -402,6 +473,7 @@ __device__ __forceinline__ void p2f_permute(u64 s[12]) {
       p2f_external<false>(s, nullptr);
     }
   }
+#endif
   // ---- internal rounds, all values scaled by c_r = 2 * 8^r ----
   // X' = 8 * (diag * X + sum), integer diagonal [-16, 8, 16, 4, 24, 32, -4, -24, -32, 2, -2, 1].  Elements (3,6), (4,7), (5,8),
   // (9,10) have diagonals (+k, -k): with h = (X_i + X_j) / 2 and b = X_i - X_j one round is h' = (k/2) b + s8, b' = 2 k h, so
@@ -409,7 +481,11 @@ __device__ __forceinline__ void p2f_permute(u64 s[12]) {
   // is all a round does for a pair -- one shift-add per part instead of two shifts, an addition and a subtraction -- and after the
   // last round X_i = h(22) + k h(21), X_j = h(22) - k h(21).  The factor 2 in c_r makes h(0) = x_i + x_j an integer sum.
   // Round 0 takes the TRUE state (its constants: P2G_ARK[0] = ark_0, P2G_K[0] = c_0 = 2).
+#if P2F_RC_ADDEND
+  u64 t0 = s[0];  // ark_0 came through the last layer (P2F_EXT_K row 3)
+#else
   u64 t0 = p2f_add_canon(s[0], p2c::P2G_ARK[0]);
+#endif
   u64 X1L, X1H, X2L, X2H, X11L, X11H;
   u64 AL[4], AH[4], BL[4], BH[4];  // pair q: A = h(even round), B = h(odd round)
   {
@@ -531,7 +607,11 @@ __device__ __forceinline__ void p2f_permute(u64 s[12]) {
     u64 x[4], k[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) { x[i] = s[g + i]; k[i] = p2c::P2G_DESCALE; }
+#if P2F_RC_ADDEND
+    p2f_mulN<4, false, true>(x, x, k, p2c::P2F_TERM0_K + 2 * g);
+#else
     p2f_mulN<4>(x, x, k);
+#endif
 #pragma unroll
     for (int i = 0; i < 4; i++) s[g + i] = x[i];
   }
@@ -539,24 +619,52 @@ __device__ __forceinline__ void p2f_permute(u64 s[12]) {
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = p2f_mul(s[i], p2c::P2G_DESCALE);
 #endif
+#if !P2F_RC_ADDEND
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = p2f_add_canon(s[i], p2c::P2_ARK_EXT_TERMINAL[i]);
+#endif
+  // the loop is left between the S-box layer and the linear layer of the last round: ONE S-box layer in the code, and the last
+  // linear layer outside the loop, where the caller's p2f_tail<OUT> drops what it does not use
 #pragma unroll 1
-  for (int r = 0; r < 4; r++) {
+  for (int r = 0;; r++) {
+#if P2F_RC_ADDEND
+    p2f_sbox12<true>(s, p2c::P2F_EXT_K + 24 * (4 + r));
+    if (r == 3) break;
+    p2f_external<false>(s, nullptr);
+#else
     p2f_sbox12(s);
-    if (r < 3) {
-      p2f_external<true>(s, p2c::P2_ARK_EXT_TERMINAL + 12 * (r + 1));
-    } else {
-      p2f_external<false>(s, nullptr);
-    }
+    if (r == 3) break;
+    p2f_external<true>(s, p2c::P2_ARK_EXT_TERMINAL + 12 * (r + 1));
+#endif
   }
+}
+// The last linear layer.  OUT says what the caller reads afterwards:
+//   P2F_ALL       all twelve elements, canonical;
+//   P2F_DIGEST    elements 0..3 canonical (a final sponge step, a compression), the rest unspecified;
+//   P2F_CAPACITY  elements 8..11 as any representative below 2^64 (an intermediate sponge step: overwrite mode replaces 0..7 and
+//                 the next permutation takes any 64-bit values), the rest unspecified.
+template <int OUT>
+__device__ __forceinline__ void p2f_tail(u64 s[12]) {
+  constexpr int O = P2F_TAILS ? OUT : (int)P2F_ALL;
+  p2f_external<false, O>(s, nullptr);
+  if constexpr (O != P2F_CAPACITY) {
 #pragma unroll
-  for (int i = 0; i < 12; i++) s[i] = gl_canon(s[i]);
+    for (int i = 0; i < 12; i++)
+      if (p2f_out_has(O, i)) s[i] = gl_canon(s[i]);
+  }
+}
+__device__ __forceinline__ void p2f_permute(u64 s[12]) {
+  p2f_body(s);
+  p2f_tail<P2F_ALL>(s);
 }
 
 #else
 // host pass: kernels are only parsed, never code-generated
+enum { P2F_ALL = 0, P2F_DIGEST = 1, P2F_CAPACITY = 2 };
 __device__ void p2f_permute(u64 s[12]);
+__device__ void p2f_body(u64 s[12]);
+template <int OUT>
+__device__ void p2f_tail(u64 s[12]);
 __device__ u64 p2f_mul(u64 a, u64 b);
 __device__ u64 p2f_mul_nv(u64 a, u64 b);
 __device__ u64 p2f_mul_k(u64 a, u64 k);
