@@ -6,7 +6,7 @@
 use core::ffi::{c_char, c_double, c_int, c_long, c_void};
 
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0] } )* } }
-opaque!(mh_ctx, mh_trace, mh_tree, mh_air, mh_proof, mh_shard, mh_lookup, mh_session, mh_miden, mh_precompile);
+opaque!(mh_ctx, mh_trace, mh_tree, mh_air, mh_proof, mh_shard, mh_lookup, mh_session, mh_miden, mh_precompile, mh_pcs);
 
 pub const MH_OK: c_int = 0;
 pub const MH_ERR_INVALID: c_int = 1;
@@ -99,6 +99,18 @@ pub struct mh_session_shape_t {
     pub log_lde_height: c_int,
     pub num_randomness: usize,
     pub num_aux_values: usize,
+    pub ood_width: usize,
+    pub num_fri_rounds: c_int,
+    pub final_poly_len: usize,
+}
+
+/// mh_pcs_*: the largest number of points one standalone opening takes
+pub const MH_PCS_MAX_POINTS: c_int = 4;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct mh_pcs_shape_t {
+    pub log_lde_height: c_int,
+    pub n_points: c_int,
     pub ood_width: usize,
     pub num_fri_rounds: c_int,
     pub final_poly_len: usize,
@@ -201,6 +213,29 @@ unsafe extern "C" {
     pub fn mh_session_fri_fold(s: *mut mh_session, beta: *const u64) -> c_int;
     pub fn mh_session_fri_final(s: *mut mh_session, coeffs_out: *mut u64) -> c_int;
     pub fn mh_session_open(s: *mut mh_session, indices: *const u64, n_indices: usize, out: *mut *mut mh_proof) -> c_int;
+    /// out: room for `cap` borrowed trees, group order [preprocessed?, main, aux, quotient]; valid once the quotient is committed
+    pub fn mh_session_trees(s: *const mh_session, out: *mut *const mh_tree, cap: c_int, n_trees: *mut c_int) -> c_int;
+    // ---- the PCS on its own: pcs::open_with_channel / pcs::verify_aligned over any trees and 1..=4 points ----
+    /// host only: 1 = z = [c0, c1] is nonzero, outside H and outside gK
+    pub fn mh_pcs_point_ok(log_max_trace_height: c_int, log_blowup: c_int, z: *const u64) -> c_int;
+    /// borrows the trees; points = [n_points][2]
+    pub fn mh_pcs_begin(ctx: *mut mh_ctx, params: *const mh_pcs_params, n_trees: c_int, trees: *const *const mh_tree, n_points: c_int, points: *const u64, out: *mut *mut mh_pcs) -> c_int;
+    pub fn mh_pcs_free(p: *mut mh_pcs);
+    pub fn mh_pcs_shape(p: *const mh_pcs, out: *mut mh_pcs_shape_t) -> c_int;
+    /// evals_out = [n_points][ood_width][2], transcript order
+    pub fn mh_pcs_evals(p: *mut mh_pcs, evals_out: *mut u64) -> c_int;
+    pub fn mh_pcs_deep(p: *mut mh_pcs, alpha: *const u64, beta: *const u64) -> c_int;
+    /// parity/debug: [2^log_lde_height][2], domain order
+    pub fn mh_pcs_download_deep(p: *mut mh_pcs, out: *mut u64) -> c_int;
+    pub fn mh_pcs_fri_commit(p: *mut mh_pcs, root: *mut u64) -> c_int;
+    pub fn mh_pcs_fri_fold(p: *mut mh_pcs, beta: *const u64) -> c_int;
+    pub fn mh_pcs_fri_final(p: *mut mh_pcs, coeffs_out: *mut u64) -> c_int;
+    /// hints only, like mh_session_open
+    pub fn mh_pcs_query(p: *mut mh_pcs, indices: *const u64, n_indices: usize, out: *mut *mut mh_proof) -> c_int;
+    /// one shot, library-owned transcript; the roots are the caller's to bind (pre_observe)
+    pub fn mh_pcs_open(ctx: *mut mh_ctx, params: *const mh_pcs_params, n_trees: c_int, trees: *const *const mh_tree, n_points: c_int, points: *const u64, challenger_state: *const u64, pre_observe: *const u64, n_pre_observe: usize, out: *mut *mut mh_proof) -> c_int;
+    /// host only; roots = [n_trees][4], widths = unpadded, all trees flat; evals_out may be null
+    pub fn mh_pcs_verify(lmcs: c_int, salt_elems: c_int, params: *const mh_pcs_params, n_trees: c_int, roots: *const u64, log_tree_heights: *const u8, n_mats: *const c_int, widths: *const usize, n_points: c_int, points: *const u64, challenger_state: *const u64, pre_observe: *const u64, n_pre_observe: usize, fields: *const u64, n_fields: usize, commitments: *const u64, n_commitments: usize, evals_out: *mut u64, digest: *mut u64, err: *mut c_char, err_cap: usize) -> c_int;
     pub fn mh_grind(ctx: *mut mh_ctx, state: *const u64, pending: *const u64, n_pending: usize, bits: c_int, witness: *mut u64) -> c_int;
     pub fn mh_grind_bytes(ctx: *mut mh_ctx, input: *const u8, n_input: usize, bits: c_int, witness: *mut u64) -> c_int;
     pub fn mh_verify(params: *const mh_pcs_params, n_airs: c_int, air_blobs: *const *const u64, air_blob_words: *const usize, log_trace_heights: *const u8, public_values: *const u64, n_public_values: usize, challenger_state: *const u64, pre_observe: *const u64, n_pre_observe: usize, fields: *const u64, n_fields: usize, commitments: *const u64, n_commitments: usize, preprocessed_root: *const u64, digest: *mut u64, err: *mut c_char, err_cap: usize) -> c_int;

@@ -154,7 +154,9 @@ void mh_blake3(const uint8_t* data, size_t n, uint8_t out32[32]);
 
 /* commit_traces (crates/lifted-stark/src/prover/commit.rs:142-180): per trace (proof order =
  * ascending height) coset-LDE by 2^log_blowup on the canonical shift of ITS lde order, then the
- * aligned LMCS tree (Lmcs::build_aligned_tree, lmcs/config.rs:125-137).  root = 4 felts. */
+ * aligned LMCS tree (Lmcs::build_aligned_tree, lmcs/config.rs:125-137).  root = 4 felts.
+ * The tree keeps its LDEs: mh_pcs_open / mh_pcs_begin open one or several such trees at 1..4 out-of-domain points and prove the
+ * evaluations (the polynomial commitment scheme on its own, no AIR), mh_pcs_verify checks them. */
 int mh_commit_traces(mh_ctx* ctx, int n_traces, mh_trace* const* traces, int log_blowup, mh_tree** out,
                      uint64_t root[4]);
 /* mh_commit_traces' root on the CPU: HOST ONLY (no context, no HIP call), for verifiers and setup.  The root of an AIR's preprocessed
@@ -416,6 +418,85 @@ int mh_grind(mh_ctx* ctx, const uint64_t state[12], const uint64_t* pending, siz
  * LAST eight digest bytes (last byte lowest: HashChallenger pops from the end) has `bits` low zero bits.  The caller replays
  * check_witness on its own challenger. */
 int mh_grind_bytes(mh_ctx* ctx, const uint8_t* input, size_t n_input, int bits, uint64_t* witness);
+/* ---- the polynomial commitment scheme on its own: open committed trees at N points ---------------------------------
+ * pcs::open_with_channel (crates/lifted-stark/src/pcs/prover.rs:34-101) and pcs::verify_aligned (pcs/verifier.rs:72-174) for ANY
+ * committed LMCS trees (mh_commit_traces; a session's own through mh_session_trees) and ANY 1 <= N <= MH_PCS_MAX_POINTS out-of-domain
+ * points -- the shape of pcs/tests.rs and benches/pcs.rs, and of a p3-style Pcs::open over this backend.  mh_prove runs the same
+ * protocol welded to the STARK (trees [preprocessed?, main, aux, quotient], points (z, z * w_N)).
+ * Semantics (pcs/deep/interpolate.rs:87-204, pcs/deep/prover.rs:115-315): with N_max the tallest matrix height over all trees, a matrix
+ * of height n = N_max / L is evaluated at z_j^L (its lifted polynomial f(X^L) at z_j); a point's evaluations are the matrices of all
+ * trees in order, each zero-padded to the LMCS alignment (8; 1 under Blake3; 17 under Keccak) -- `ood_width` EF values; column i of
+ * that flat aligned order carries alpha^(ood_width - 1 - i), point j carries beta^j:
+ *   Q(x) = sum_j beta^j (f_red(z_j) - f_red(x)) / (z_j - x),   f_red = sum_i alpha^(ood_width - 1 - i) f_i.
+ * Duplicate points are legal.  The FRI rounds, grinding and the query phase are those of mh_prove; a tree shorter than the tallest is
+ * virtually lifted in the query phase (its indices fold by their low bits, lmcs/tree_indices.rs:72-84).
+ * Preconditions, MH_ERR_INVALID with a message otherwise and before anything is launched (pcs/deep/prover.rs:68-79, :133-138):
+ * n_trees >= 1; every tree was committed on this context under its current LMCS hasher and salt width with
+ * log_blowup == params->log_blowup; at least one tree at the maximum height; 1 <= n_points <= MH_PCS_MAX_POINTS; every point nonzero,
+ * outside the trace domain H of the tallest matrix and outside the LDE coset gK (mh_pcs_point_ok; domain.rs:539-553).  Single GPU
+ * only: a tree from mh_commit_traces_sharded (world > 1) is refused.  Salted trees (mh_ctx_set_salt) are accepted; the FRI round trees
+ * then take the context's salt as in mh_prove.  The trees are BORROWED: they must outlive the mh_pcs.
+ * BINDING THE ROOTS IS THE CALLER'S JOB (pcs/tests.rs:69-72 observes them before opening): neither mh_pcs_open nor mh_pcs_verify
+ * puts the roots into the transcript.  Passing each root's four words in `pre_observe`, to both, binds them under all five
+ * configurations (a byte configuration's words go in as the digest's 32 raw bytes).
+ *
+ * Staged (the caller owns the transcript; calls out of order return MH_ERR_INVALID, as in the session):
+ *   begin(trees, points)     checks the preconditions
+ *   evals -> [n_points][ood_width] EF    per point in order: channel.send_algebra_slice     pcs/deep/prover.rs:88-113
+ *   [grind deep_pow_bits]  deep(alpha, beta)                                                deep/prover.rs:147-193
+ *   num_fri_rounds x { fri_commit -> root, [grind folding_pow_bits], fri_fold(beta) }       fri/prover.rs:113-205
+ *   fri_final -> final_poly_len coefficients, descending degree                             fri/prover.rs:212-239
+ *   [grind query_pow_bits]  query(indices) -> hints: every input tree in order, then every FRI round   pcs/prover.rs:138-195 */
+#define MH_PCS_MAX_POINTS 4
+typedef struct mh_pcs mh_pcs;
+typedef struct mh_pcs_shape_t {
+  int log_lde_height;    /* of the tallest tree: query indices are sampled with this many bits */
+  int n_points;
+  size_t ood_width;      /* EF evaluations per point: every matrix of every tree, each padded to the LMCS alignment */
+  int num_fri_rounds;
+  size_t final_poly_len; /* EF coefficients of the final polynomial */
+} mh_pcs_shape_t;
+/* Host only.  1 = z may be opened at when the tallest committed matrix has 2^log_max_trace_height rows, 0 = not (or bad arguments). */
+int mh_pcs_point_ok(int log_max_trace_height, int log_blowup, const uint64_t z[2]);
+int mh_pcs_begin(mh_ctx* ctx, const mh_pcs_params* params, int n_trees, const mh_tree* const* trees, int n_points,
+                 const uint64_t* points /* [n_points][2] */, mh_pcs** out);
+void mh_pcs_free(mh_pcs* p);
+int mh_pcs_shape(const mh_pcs* p, mh_pcs_shape_t* out);
+int mh_pcs_evals(mh_pcs* p, uint64_t* evals_out /* [n_points][ood_width][2], transcript order */);
+int mh_pcs_deep(mh_pcs* p, const uint64_t alpha[2], const uint64_t beta[2]);
+/* Parity/debug: the DEEP layer Q, [2^log_lde_height][2] in DOMAIN order (index i <-> x = g * w_K^i); valid between deep and the
+ * first fold. */
+int mh_pcs_download_deep(mh_pcs* p, uint64_t* out);
+int mh_pcs_fri_commit(mh_pcs* p, uint64_t root[4]);
+int mh_pcs_fri_fold(mh_pcs* p, const uint64_t beta[2]);
+int mh_pcs_fri_final(mh_pcs* p, uint64_t* coeffs_out);
+/* The result holds only the hints, like mh_session_open. */
+int mh_pcs_query(mh_pcs* p, const uint64_t* indices, size_t n_indices, mh_proof** out);
+/* One shot with the library's transcript (all five configurations, like mh_prove), exactly open_with_channel's:
+ *   for each point j in order: send_algebra_slice(point j's aligned evaluations);  grind deep_pow_bits;  sample alpha, then beta;
+ *   per FRI round: send the commitment, grind folding_pow_bits, sample beta;  the final polynomial (descending degree);
+ *   grind query_pow_bits;  num_queries x sample_bits(log_lde_height);  hint every input tree's batch opening in tree order, then every
+ *   FRI round's;  finalize.
+ * mh_proof_fields / mh_proof_commitments are the transcript, mh_proof_digest its digest; mh_proof_log_trace_heights lists the trees'
+ * log heights (tallest matrix of each). */
+int mh_pcs_open(mh_ctx* ctx, const mh_pcs_params* params, int n_trees, const mh_tree* const* trees, int n_points, const uint64_t* points,
+                const uint64_t challenger_state[12], const uint64_t* pre_observe, size_t n_pre_observe, mh_proof** out);
+/* verify_aligned.  Host only: no GPU, no ctx.  roots: [n_trees][4]; log_tree_heights[t]: log2 of the rows of tree t's tallest matrix
+ * (its depth is that + params->log_blowup); n_mats[t] matrices per tree, whose UNPADDED widths follow each other in `widths`, all trees
+ * flat; salt_elems: the salt width the trees were committed with (0: the plain LMCS).  MH_OK + the transcript digest + (evals_out not
+ * NULL) the evaluations with the alignment padding dropped, [n_points][sum of the widths][2]; or MH_ERR_INVALID with the reason in
+ * `err`: a malformed or truncated stream, trailing data, a non-canonical felt, a point on H or gK, n_points or n_trees out of range,
+ * an opening that does not match its root, a DEEP / FRI inconsistency. */
+int mh_pcs_verify(int lmcs, int salt_elems, const mh_pcs_params* params, int n_trees, const uint64_t* roots,
+                  const uint8_t* log_tree_heights, const int* n_mats, const size_t* widths, int n_points, const uint64_t* points,
+                  const uint64_t challenger_state[12], const uint64_t* pre_observe, size_t n_pre_observe, const uint64_t* fields,
+                  size_t n_fields, const uint64_t* commitments, size_t n_commitments, uint64_t* evals_out, uint64_t digest[4], char* err,
+                  size_t err_cap);
+/* The session's input trees in group order [preprocessed?, main, aux, quotient] (prover/mod.rs:552-560), BORROWED until
+ * mh_session_free (the preprocessed tree: until its owner frees it); valid once the quotient is committed.  *n_trees = their number;
+ * MH_ERR_INVALID if cap is smaller. */
+int mh_session_trees(const mh_session* s, const mh_tree** out, int cap, int* n_trees);
+
 /* ---- verifier (host only: no GPU, no ctx) ---------------------------------------------------------------------
  * Replays a proof against the AIRs' constraint-DAG blobs: crates/lifted-stark/src/verifier/mod.rs (flow, constraint
  * identity), pcs/verifier.rs + lmcs/config.rs:172-211 (openings), pcs/deep/verifier.rs, pcs/fri/verifier.rs.

@@ -41,9 +41,12 @@ EXPORTS = [
     "mh_check_balance", "mh_check_balance_miden", "mh_check_balance_miden_traces", "mh_check_balance_precompile", "mh_check_balance_precompile_traces",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
+    "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
+    "mh_pcs_fri_fold", "mh_pcs_fri_final", "mh_pcs_query", "mh_pcs_open", "mh_pcs_verify", "mh_session_trees",
 ]
 
 MH_MAX_SALT_ELEMS = 8  # mh_ctx_set_salt: the largest salt width of the hiding LMCS
+MH_PCS_MAX_POINTS = 4  # mh_pcs_*: the largest number of points one opening takes
 
 # the in-tree cache of precompiled constraint kernels (filled by __graft_entry__.build() / tools/jit_precompile.py); $MH_JIT_CACHE_DIR wins
 # It is consulted READ-ONLY ($MH_JIT_CACHE_RO_DIR): kernels this box has to compile itself (another hiprtc version, another AIR) go to
@@ -211,6 +214,19 @@ def load_library():
     lib.mh_air_log_quotient_degree.argtypes = [C.c_void_p]
     lib.mh_proof_free.argtypes = [C.c_void_p]
     lib.mh_session_free.argtypes = [C.c_void_p]
+    lib.mh_pcs_free.argtypes = [C.c_void_p]
+    lib.mh_pcs_point_ok.argtypes = [C.c_int, C.c_int, u64p]
+    lib.mh_pcs_shape.argtypes = [C.c_void_p, C.c_void_p]
+    for name in ("mh_pcs_evals", "mh_pcs_download_deep", "mh_pcs_fri_commit", "mh_pcs_fri_fold", "mh_pcs_fri_final"):
+        getattr(lib, name).argtypes = [C.c_void_p, u64p]
+    lib.mh_pcs_deep.argtypes = [C.c_void_p, u64p, u64p]
+    lib.mh_pcs_query.argtypes = [C.c_void_p, u64p, C.c_size_t, C.POINTER(C.c_void_p)]
+    lib.mh_pcs_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, u64p, C.POINTER(C.c_void_p)]
+    lib.mh_pcs_open.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, u64p, u64p, u64p, C.c_size_t,
+                                C.POINTER(C.c_void_p)]
+    lib.mh_pcs_verify.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, u64p, C.POINTER(C.c_uint8), C.POINTER(C.c_int), C.POINTER(C.c_size_t),
+                                  C.c_int, u64p, u64p, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, u64p, u64p, C.c_char_p, C.c_size_t]
+    lib.mh_session_trees.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]
     for name in ("mh_session_shape", "mh_session_commit_main", "mh_session_commit_aux", "mh_session_commit_quotient",
                  "mh_session_ood_point_ok", "mh_session_ood", "mh_session_deep", "mh_session_fri_commit",
                  "mh_session_fri_fold", "mh_session_fri_final", "mh_session_open"):
@@ -848,6 +864,14 @@ class Session:
         self.ctx.check(self.lib.mh_session_open(self.h, _ptr(idx), C.c_size_t(idx.size), C.byref(h)))
         return Proof(self.lib, h)
 
+    def trees(self):
+        """mh_session_trees: the session's input trees in group order [preprocessed?, main, aux, quotient] as raw handles (c_void_p),
+        BORROWED -- valid until the session is freed, never to be freed by the caller; for PcsOpening / pcs_open.  Available once the
+        quotient is committed."""
+        arr, n = (C.c_void_p * 8)(), C.c_int(0)
+        self.ctx.check(self.lib.mh_session_trees(self.h, arr, 8, C.byref(n)))
+        return [C.c_void_p(arr[i]) for i in range(n.value)]
+
     def free(self):
         if getattr(self, "h", None):
             self.lib.mh_session_free(self.h)
@@ -858,6 +882,139 @@ class Session:
             self.free()
         except Exception:
             pass
+
+
+# ---- the polynomial commitment scheme on its own (pcs::open_with_channel / pcs::verify_aligned) ----------------
+class PcsShape(C.Structure):
+    _fields_ = [("log_lde_height", C.c_int), ("n_points", C.c_int), ("ood_width", C.c_size_t), ("num_fri_rounds", C.c_int),
+                ("final_poly_len", C.c_size_t)]
+
+
+def _tree_handles(trees):
+    """LmcsTree / Committed objects or raw handles (Session.trees()) -> a C array of mh_tree*."""
+    hs = []
+    for t in trees:
+        t = t.tree() if isinstance(t, Committed) else t
+        hs.append(t.h if isinstance(t, LmcsTree) else t)
+    return (C.c_void_p * max(1, len(hs)))(*hs)
+
+
+def _points(points):
+    return _arr([int(x) for z in points for x in z] or [0])
+
+
+def pcs_point_ok(log_max_trace_height, log_blowup, z):
+    """mh_pcs_point_ok (host only): z = (c0, c1) is nonzero, outside the trace domain H of the tallest matrix and outside the LDE coset gK."""
+    zz = _arr([int(z[0]), int(z[1])])
+    return bool(load_library().mh_pcs_point_ok(int(log_max_trace_height), int(log_blowup), _ptr(zz)))
+
+
+class PcsOpening:
+    """mh_pcs: committed trees opened at 1..4 points, one method per step of pcs::open_with_channel (crates/lifted-stark/src/pcs/
+    prover.rs:34-101), for a caller-owned transcript.  trees: LmcsTree / Committed objects (or Session.trees() handles), borrowed for
+    the opening's lifetime; points: [(c0, c1), ...].  EF values are (c0, c1) tuples."""
+
+    def __init__(self, ctx, trees, points, params):
+        self.ctx, self.lib = ctx, ctx.lib
+        self._keep = list(trees)
+        self.params = params if isinstance(params, PcsParams) else PcsParams.from_dict(params)
+        pts = _points(points)
+        h = C.c_void_p()
+        ctx.check(self.lib.mh_pcs_begin(ctx.h, C.byref(self.params), len(self._keep), _tree_handles(self._keep), len(points), _ptr(pts),
+                                        C.byref(h)))
+        self.h = h
+        ctx._children.add(self)
+        self.shape = PcsShape()
+        ctx.check(self.lib.mh_pcs_shape(self.h, C.byref(self.shape)))
+
+    def evals(self):
+        """-> uint64 [n_points, ood_width, 2]: per point the aligned evaluations of every matrix of every tree, transcript order."""
+        out = np.zeros((self.shape.n_points, self.shape.ood_width, 2), dtype=np.uint64)
+        self.ctx.check(self.lib.mh_pcs_evals(self.h, _ptr(out)))
+        return out
+
+    def deep(self, alpha, beta):
+        a, b = Session._e(alpha), Session._e(beta)
+        self.ctx.check(self.lib.mh_pcs_deep(self.h, _ptr(a), _ptr(b)))
+
+    def download_deep(self):
+        """-> uint64 [2^log_lde_height, 2]: the DEEP layer in domain order (index i <-> x = g * w_K^i)."""
+        out = np.zeros((1 << self.shape.log_lde_height, 2), dtype=np.uint64)
+        self.ctx.check(self.lib.mh_pcs_download_deep(self.h, _ptr(out)))
+        return out
+
+    def fri_commit(self):
+        root = np.zeros(4, dtype=np.uint64)
+        self.ctx.check(self.lib.mh_pcs_fri_commit(self.h, _ptr(root)))
+        return root
+
+    def fri_fold(self, beta):
+        b = Session._e(beta)
+        self.ctx.check(self.lib.mh_pcs_fri_fold(self.h, _ptr(b)))
+
+    def fri_final(self):
+        out = np.zeros(2 * self.shape.final_poly_len, dtype=np.uint64)
+        self.ctx.check(self.lib.mh_pcs_fri_final(self.h, _ptr(out)))
+        return out
+
+    def query(self, indices):
+        """-> Proof carrying only the hinted fields / commitments (every input tree in order, then every FRI round)."""
+        idx = _arr([int(i) for i in indices])
+        h = C.c_void_p()
+        self.ctx.check(self.lib.mh_pcs_query(self.h, _ptr(idx), C.c_size_t(idx.size), C.byref(h)))
+        return Proof(self.lib, h)
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.lib.mh_pcs_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def pcs_open(ctx, trees, points, params, challenger_state, pre_observe):
+    """mh_pcs_open: the whole opening with the library's transcript -> Proof (fields, commitments, digest).  The roots are NOT observed
+    by the library: put them into pre_observe (four words per root), here and in pcs_verify."""
+    keep = list(trees)
+    p = params if isinstance(params, PcsParams) else PcsParams.from_dict(params)
+    pts, st, pre = _points(points), _arr(challenger_state), _arr(list(pre_observe) or [0])
+    h = C.c_void_p()
+    ctx.check(ctx.lib.mh_pcs_open(ctx.h, C.byref(p), len(keep), _tree_handles(keep), len(points), _ptr(pts), _ptr(st), _ptr(pre),
+                                  C.c_size_t(len(pre_observe)), C.byref(h)))
+    return Proof(ctx.lib, h)
+
+
+def pcs_verify(roots, log_tree_heights, widths, points, params, challenger_state, pre_observe, fields, commitments, lmcs="poseidon2",
+               salt_elems=0):
+    """mh_pcs_verify (host only, no GPU): roots[t] = tree t's four words, log_tree_heights[t] = log2 rows of its tallest matrix,
+    widths[t] = the unpadded widths of its matrices.  Returns (True, digest, evals uint64 [n_points, sum of widths, 2]) or
+    (False, message, None)."""
+    lib = load_library()
+    n = len(roots)
+    r = _arr(np.asarray(roots, dtype=np.uint64).reshape(-1) if n else [0])
+    lh = (C.c_uint8 * max(1, n))(*[int(x) for x in log_tree_heights])
+    nm = (C.c_int * max(1, n))(*[len(w) for w in widths])
+    flat = [int(w) for ws in widths for w in ws]
+    ws = (C.c_size_t * max(1, len(flat)))(*flat)
+    p = params if isinstance(params, PcsParams) else PcsParams.from_dict(params)
+    pts, st, pre = _points(points), _arr(challenger_state), _arr(list(pre_observe) or [0])
+    f = _arr(fields if len(fields) else [0])
+    cm = _arr(np.asarray(commitments, dtype=np.uint64).reshape(-1))
+    cm = cm if cm.size else _arr([0])
+    n_cm = np.asarray(commitments).size // 4
+    ok_n = 1 <= len(points) <= MH_PCS_MAX_POINTS
+    evals = np.zeros((len(points) if ok_n else 1, max(1, sum(flat)), 2), dtype=np.uint64)
+    digest, err = np.zeros(4, dtype=np.uint64), C.create_string_buffer(512)
+    rc = lib.mh_pcs_verify(Ctx.LMCS[lmcs], int(salt_elems), C.byref(p), n, _ptr(r), lh, nm, ws, len(points), _ptr(pts), _ptr(st), _ptr(pre),
+                           C.c_size_t(len(pre_observe)), _ptr(f), C.c_size_t(len(fields)), _ptr(cm), C.c_size_t(n_cm), _ptr(evals),
+                           _ptr(digest), err, C.c_size_t(512))
+    if rc != 0:
+        return False, err.value.decode(), None
+    return True, digest, evals[:, :sum(flat)]
 
 
 def grind(ctx, state, pending, bits):

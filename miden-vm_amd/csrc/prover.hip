@@ -15,6 +15,7 @@
 #include "ctx.hpp"
 #include "gl.cuh"
 #include "kernels.hpp"
+#include "pcs_stage.hpp"
 #include "poseidon2.cuh"
 #include <algorithm>
 #include <chrono>
@@ -356,20 +357,8 @@ static mh_tree* commit_traces_dist(mh_ctx* c, const std::vector<const mh_trace*>
 }
 
 // -------------------------------------------------------------------------------------------------
-struct mh_proof {
-  std::vector<uint8_t> log_trace_heights;  // instance order
-  std::vector<u64> fields;
-  std::vector<u64> commitments;  // 4 felts each
-  u64 digest[4];
-};
-
+// mh_proof, fri_num_rounds: pcs_stage.hpp (shared with the standalone PCS, pcs_open.hip)
 static size_t align8(size_t w) { return (w + 7) / 8 * 8; }
-
-static int fri_num_rounds(const mh_pcs_params& p, int log_lde) {
-  int log_max_final = p.log_final_degree + p.log_blowup;
-  int steps = log_lde > log_max_final ? log_lde - log_max_final : 0;
-  return (steps + p.log_folding_arity - 1) / p.log_folding_arity;
-}
 
 // One proof in flight: every device stage of `prove` (prover/mod.rs:230-578) as a method that takes the
 // challenges the transcript produced and returns the values the transcript must observe next.  mh_prove
@@ -412,12 +401,9 @@ struct mh_session {
   size_t W = 0;
   e2 z, z_next;
   std::vector<e2> ev0, ev1;
-  // FRI
-  DevBuf layer;
-  std::vector<std::unique_ptr<mh_tree>> fri_trees;
-  int rounds = 0, log_rows = 0, cbits = 0, cb_loc = 0;
-  size_t fri_c0 = 0;
-  bool sharded = false, round_committed = false;
+  // FRI rounds and the query phase: shared with the standalone PCS (pcs_stage.hpp)
+  PcsStage fs;
+  int rounds = 0;
 
   void begin(mh_ctx* ctx, const mh_pcs_params& params, int n, mh_air* const* airs_in, mh_trace* const* traces_in,
              const u64* publics_in, size_t n_publics, const Dist& d) {
@@ -497,6 +483,7 @@ struct mh_session {
       MH_REQUIRE(prep_tree->salt.n == c->salt.n, "the preprocessed (setup) tree was committed with another salt width than this context's (mh_ctx_set_salt)");
     }
     rounds = fri_num_rounds(pp, L);
+    fs.c = c; fs.pp = pp; fs.dist = dist; fs.lb = lb; fs.L = L; fs.rounds = rounds;
     stage = 1;
   }
   // aligned_len(w, lmcs.alignment()) (util/align.rs:7-13): the sponge's rate -- 8 (Poseidon2), 17 (Keccak) -- or 1 for the chaining
@@ -778,159 +765,46 @@ struct mh_session {
       negc[i] = pw;
       pw = e2_mul(pw, alpha_d);
     }
-    layer.alloc((N << lbl) * 16);
+    fs.layer.alloc((N << lbl) * 16);
     // Q has degree < N, so one coset determines it: assemble there, extend by LDE (deep.hip).  MH_DEEP_ALL_COSETS=1 keeps the
     // assemble kernel on every coset (the reference path of tests/test_gpu_deep_one_coset.py); read per call, never cached.
     const char* all_env = getenv("MH_DEEP_ALL_COSETS");
     const bool one_coset = !(all_env && atoi(all_env)) && lbl >= 1 && log_N >= DEEP_ONE_COSET_MIN_LOG_N;
-    deep_assemble(c, mats, coef_off, log_N, lb, negc, z, z_next, fred0, fred1, beta_d, layer.u(), one_coset);
-    // cbits = coset bits of the whole layer, cb_loc = those stored on this rank (cosets fri_c0 ..)
-    log_rows = log_N; cbits = lb; cb_loc = lbl; fri_c0 = coset0;
-    sharded = dist.on();
+    deep_assemble(c, mats, coef_off, log_N, lb, negc, z, z_next, fred0, fred1, beta_d, fs.layer.u(), one_coset);
+    fs.start(log_N, lbl, coset0);
     stage = 6;
   }
-  // ---- 8. FRI: commit the current layer, then fold it ----
+  // ---- 8. FRI and 9. the query phase: pcs_stage.hpp ----
   void fri_commit(u64 root[4]) {
     expect(6, "fri_commit");
-    ProfScope span(c, "span:FRI round commit");  // pcs/fri/prover.rs:164
-    MH_REQUIRE((int)fri_trees.size() < rounds && !round_committed, "no FRI round left to commit");
-    const int la = pp.log_folding_arity;
-    if (sharded && log_rows - la < dist.logG) {
-      // fewer leaf rows per coset than ranks: the row-range split of the tree is over; every rank takes
-      // the whole (small) layer and continues redundantly
-      DevBuf full(((size_t)1 << (log_rows + cbits)) * 16);
-      dist.all_gather(c, layer.p, full.p, ((size_t)1 << (log_rows + cb_loc)) * 16);
-      layer = std::move(full);
-      cb_loc = cbits;
-      fri_c0 = 0;
-      sharded = false;
-    }
-    if (log_rows < la) {  // tiny layer: fewer than `arity` rows per coset -> single-coset (natural) layout
-      MH_REQUIRE(!sharded, "internal: sharded FRI layer shorter than the arity");
-      DevBuf nat(((size_t)1 << (log_rows + cbits)) * 16);
-      fri_to_natural(c, layer.u(), log_rows, cbits, nat.u());
-      c->sync();
-      layer = std::move(nat);
-      log_rows += cbits;
-      cbits = 0;
-      cb_loc = 0;
-    }
-    std::unique_ptr<mh_tree> t(new mh_tree());
-    t->ctx = c; t->log_blowup = cbits;
-    t->fri_log_rows = log_rows; t->fri_log_arity = la;
-    t->fri_log_cosets = cb_loc; t->fri_coset0 = fri_c0;
-    if (sharded) {
-      DevBuf dig(((size_t)1 << (log_rows - la + cb_loc)) * 32);
-      fri_leaf_hash(c, layer.u(), log_rows, cb_loc, la, dig.u());
-      lmcs_build_sharded(c, t.get(), dist, dig.u(), log_rows - la);
-    } else {
-      lmcs_alloc_layers(t.get(), log_rows + cbits - la);
-      lmcs_salt_assign(c, t.get());
-      fri_leaf_hash(c, layer.u(), log_rows, cbits, la, lmcs_leaf_layer(t.get()), lmcs_salt_of(t.get()));
-      lmcs_compress_layers(c, t.get());
-    }
-    memcpy(root, t->root, 32);
-    fri_trees.push_back(std::move(t));
-    round_committed = true;
+    fs.fri_commit(root);
   }
   void fri_fold_round(e2 fb) {
     expect(6, "fri_fold");
-    ProfScope span(c, "span:FRI fold");  // pcs/fri/prover.rs:183
-    MH_REQUIRE(round_committed, "fold before the round's commitment");
-    const int la = pp.log_folding_arity;
-    DevBuf next(((size_t)1 << (log_rows + cb_loc - la)) * 16);
-    fri_fold(c, layer.u(), log_rows, cb_loc, cbits, fri_c0, la, fb, next.u());
-    fri_trees.back()->fri_layer = std::move(layer);
-    layer = std::move(next);
-    log_rows -= la;
-    round_committed = false;
+    fs.fri_fold_round(fb);
   }
-  // final polynomial (fri/prover.rs:212-239): it has degree < fpd = n_f / B, so the fpd evaluations on
-  // ONE coset s*<w_fpd> of the final layer determine it (s = w_{n_f}^(first local coset); s = 1 on a
-  // single GPU = the reference's first fpd bit-reversed entries).  Interpolated on the host, shift undone,
-  // returned in descending degree order.
   void fri_final(std::vector<e2>& desc) {
     expect(6, "fri_final");
-    ProfScope span(c, "span:idft final poly");  // pcs/fri/prover.rs:231
-    MH_REQUIRE((int)fri_trees.size() == rounds && !round_committed, "FRI rounds not finished");
-    const int logn_f = log_rows + cbits;
-    const int log_fpd = std::max(0, logn_f - lb);
-    const size_t fpd = (size_t)1 << log_fpd;
-    const size_t n_loc = (size_t)1 << (log_rows + cb_loc);
-    std::vector<u64> host(2 * n_loc);
-    c->d2h(host.data(), layer.p, n_loc * 16);
-    std::vector<e2> vals(fpd);
-    u64 s_shift = 1;
-    if (sharded) {
-      MH_REQUIRE(cbits == lb && fpd == ((size_t)1 << log_rows), "internal: final layer shape");
-      for (size_t r = 0; r < fpd; r++) vals[r] = e2{host[2 * r], host[2 * r + 1]};  // first local coset
-      s_shift = gl_pow(gl_two_adic_generator(logn_f), fri_c0);
-    } else {
-      for (size_t r = 0; r < fpd; r++) {
-        size_t i = r << (logn_f - log_fpd);
-        size_t slot = ((i & (((size_t)1 << cbits) - 1)) << log_rows) + (i >> cbits);
-        vals[r] = e2{host[2 * slot], host[2 * slot + 1]};
-      }
-    }
-    const u64 w_inv = gl_inv(gl_two_adic_generator(log_fpd)), n_inv = gl_inv((u64)fpd);
-    const u64 s_inv = gl_inv(s_shift);
-    std::vector<e2> coef(fpd);
-    u64 sk = 1;
-    for (size_t k = 0; k < fpd; k++) {
-      e2 s = e2_make(0);
-      u64 wk = gl_pow(w_inv, k), x = 1;
-      for (size_t r = 0; r < fpd; r++) {
-        s = e2_add(s, e2_mulf(vals[r], x));
-        x = gl_mul(x, wk);
-      }
-      coef[k] = e2_mulf(s, gl_mul(n_inv, sk));
-      sk = gl_mul(sk, s_inv);
-    }
-    desc.assign(coef.rbegin(), coef.rend());
-    layer.release();
+    fs.fri_final(desc);
     stage = 7;
   }
-  // ---- 9. openings of every tree at the sampled domain indices, in transcript (hint) order ----
-  void open(std::vector<size_t> idx, std::vector<u64>& fields, std::vector<u64>& commitments) {
+  // the input trees in group order [preprocessed?, main, aux, quotient] (prover/mod.rs:552-560); valid once the quotient is committed
+  std::vector<const mh_tree*> input_trees() const {
+    std::vector<const mh_tree*> v;
+    if (prep_tree) v.push_back(prep_tree);
+    for (const mh_tree* t : {main_tree.get(), aux_tree.get(), quot_tree.get()}) v.push_back(t);
+    return v;
+  }
+  void open(const std::vector<size_t>& idx, std::vector<u64>& fields, std::vector<u64>& commitments) {
     expect(7, "open");
-    ProfScope span(c, "span:query phase");  // pcs/prover.rs:89
-    std::sort(idx.begin(), idx.end());
-    idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
-    for (size_t i : idx) MH_REQUIRE(i < ((size_t)1 << L), "query index out of range");
-    // every tree's gather list first, then ONE gather / read-back (/ all-reduce) for all of them
-    std::vector<const u64*> ptrs;
-    std::vector<OpenPlan> plans;
-    if (prep_tree) {  // a tree shorter than the max domain is virtually lifted: indices fold by their low bits
-      std::vector<size_t> pidx(idx);
-      const size_t mask = ((size_t)1 << (prep_tree->log_height + prep_tree->shard_logG)) - 1;  // full depth (a rank stores a subtree)
-      for (auto& i : pidx) i &= mask;
-      std::sort(pidx.begin(), pidx.end());
-      pidx.erase(std::unique(pidx.begin(), pidx.end()), pidx.end());
-      plans.push_back(lmcs_open_plan(prep_tree, pidx, alignment(), &dist, ptrs));
-    }
-    for (const mh_tree* t : {main_tree.get(), aux_tree.get(), quot_tree.get()}) plans.push_back(lmcs_open_plan(t, idx, alignment(), &dist, ptrs));
-    int depth = L;
-    for (auto& t : fri_trees) {
-      depth -= pp.log_folding_arity;
-      const size_t mask = ((size_t)1 << depth) - 1;
-      for (auto& i : idx) i &= mask;
-      std::sort(idx.begin(), idx.end());
-      idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
-      plans.push_back(lmcs_open_plan(t.get(), idx, 1, &dist, ptrs));
-    }
-    std::vector<u64> host;
-    lmcs_open_run(c, ptrs, &dist, host);
-    for (const OpenPlan& plan : plans) {
-      std::vector<u64> f, cm;
-      lmcs_open_take(plan, host, f, cm);
-      fields.insert(fields.end(), f.begin(), f.end());
-      commitments.insert(commitments.end(), cm.begin(), cm.end());
-    }
+    fs.trees = input_trees();
+    fs.alignment = alignment();
+    fs.open(idx, fields, commitments);
     stage = 8;
   }
 };
 
-static void do_grind(mh_ctx* c, HostTranscript& tr, int bits) {
+void do_grind(mh_ctx* c, HostTranscript& tr, int bits) {
   if (bits == 0) {
     tr.fields.push_back(0);
     return;
@@ -1479,6 +1353,22 @@ int mh_session_open(mh_session* s, const uint64_t* indices, size_t n_indices, mh
   for (int i = 0; i < s->n_airs; i++) p->log_trace_heights.push_back((uint8_t)s->lhs[i]);
   *out = p.release();
   MH_CATCH
+}
+// The session's input trees in group order [preprocessed?, main, aux, quotient]: borrowed until mh_session_free.
+int mh_session_trees(const mh_session* s, const mh_tree** out, int cap, int* n_trees) {
+  if (!s || !n_trees || (!out && cap > 0)) return MH_ERR_INVALID;
+  if (s->stage < 4) {
+    s->c->err = "session call out of protocol order: trees (valid once the quotient is committed)";
+    return MH_ERR_INVALID;
+  }
+  const std::vector<const mh_tree*> v = s->input_trees();
+  *n_trees = (int)v.size();
+  if (cap < (int)v.size()) {
+    s->c->err = "mh_session_trees: room for fewer trees than the session holds";
+    return MH_ERR_INVALID;
+  }
+  for (size_t i = 0; i < v.size(); i++) out[i] = v[i];
+  return MH_OK;
 }
 // Proof-of-work: the smallest witness w such that observing w (after the `n_pending` absorbed-but-not-yet-
 // permuted felts) and sampling `bits` bits yields zero  (p3 GrindingChallenger::grind, any valid witness verifies).

@@ -270,9 +270,7 @@ e2 periodic_at(const std::vector<u64>& col, e2 y) {
   return acc;
 }
 
-void verify_impl(const mh_pcs_params& pp, const std::vector<DagIR>& airs, const std::vector<int>& lhs, const std::vector<u64>& publics,
-                 const u64* prep_root, Reader& rd, mh_external_assertions external, void* external_user, u64 digest[4]) {
-  const size_t n_airs = airs.size();
+void check_params(const mh_pcs_params& pp) {
   const int lb = pp.log_blowup, la = pp.log_folding_arity;
   if (lb < 1 || lb > 8 || la < 1 || la > 3 || pp.num_queries < 1) throw Reject("unsupported PCS parameters");
   // sample_bits works on the low 32 bits of a sample (random_coin.masm sample_bits): more PoW bits cannot be checked
@@ -281,6 +279,128 @@ void verify_impl(const mh_pcs_params& pp, const std::vector<DagIR>& airs, const 
   if (pp.log_final_degree < 0 || pp.log_final_degree > 32) throw Reject("log_final_degree must be in 0..32");
   // PcsParams::new (pcs/params.rs:62-69): FinalDegreeUnreachable -- the reference's verifier can only be built from valid parameters
   if (pp.log_final_degree + lb < la - 1) throw Reject("final degree unreachable by fixed-arity folding");
+}
+
+// One committed tree as the PCS verifier sees it: its root, the ALIGNED widths of its matrices and its depth (log of its LDE height).
+struct PcsGroup {
+  Digest4 root;
+  std::vector<size_t> widths;
+  int depth;
+};
+// pcs::verify_aligned (crates/lifted-stark/src/pcs/verifier.rs:72-174) over any list of committed trees and n_points >= 1 out-of-domain
+// points zs: reads, per point in order, the aligned evaluations of every tree's matrices (returned in ev[j]); the DEEP challenges; the
+// FRI commit phase; the queries; then opens every tree and every FRI round at them and checks
+//   Q(x) = sum_j beta^j (f_red(z_j) - f_red(x)) / (z_j - x)                                     (pcs/deep/verifier.rs)
+// against the FRI openings down to the final polynomial.  L = log of the LDE height of the tallest tree.  The STARK verifier calls it with
+// [preprocessed?, main, aux, quotient] and (z, z * w_N); mh_pcs_verify with the caller's trees and points.
+void pcs_verify_aligned(const mh_pcs_params& pp, int L, const std::vector<PcsGroup>& groups, const e2* zs, int n_points, Reader& rd,
+                        std::vector<e2>* ev) {
+  const int lb = pp.log_blowup, la = pp.log_folding_arity;
+  const u64 g = gl_lde_shift(L);
+  size_t W = 0;
+  for (auto& gr : groups)
+    for (size_t w : gr.widths) W += w;
+  for (int k = 0; k < n_points; k++)
+    for (size_t i = 0; i < W; i++) ev[k].push_back(rd.recv_ef());
+  rd.check_pow(pp.deep_pow_bits);
+  const e2 alpha_d = rd.ch.sample_ef(), beta_d = rd.ch.sample_ef();
+  e2 fred[MH_PCS_MAX_POINTS];
+  for (int k = 0; k < n_points; k++) {
+    e2 a = e2_make(0);
+    for (size_t i = 0; i < W; i++) a = e2_add(e2_mul(a, alpha_d), ev[k][i]);
+    fred[k] = a;
+  }
+  const int rounds = fri_rounds(pp, L);
+  std::vector<Digest4> fri_roots;
+  std::vector<e2> fri_betas;
+  for (int r = 0; r < rounds; r++) {
+    fri_roots.push_back(rd.recv_digest());
+    rd.check_pow(pp.folding_pow_bits);
+    fri_betas.push_back(rd.ch.sample_ef());
+  }
+  const size_t fpd = (size_t)1 << std::max(0, L - rounds * la - lb);
+  std::vector<e2> final_poly;  // descending degree
+  for (size_t i = 0; i < fpd; i++) final_poly.push_back(rd.recv_ef());
+  rd.check_pow(pp.query_pow_bits);
+  std::vector<size_t> idx;
+  for (int i = 0; i < pp.num_queries; i++) idx.push_back(rd.ch.sample_bits(L));
+  std::sort(idx.begin(), idx.end());
+  idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
+
+  // ---- query phase: trace openings -> DEEP quotient values (deep/verifier.rs) ----
+  std::vector<e2> reduced(idx.size(), e2_make(0));
+  for (size_t t = 0; t < groups.size(); t++) {
+    // a tree shorter than the max domain is opened at the indices' low bits (lmcs/tree_indices.rs:72-84)
+    const size_t mask = ((size_t)1 << groups[t].depth) - 1;
+    std::vector<size_t> tidx;
+    for (size_t i : idx) tidx.push_back(i & mask);
+    std::sort(tidx.begin(), tidx.end());
+    tidx.erase(std::unique(tidx.begin(), tidx.end()), tidx.end());
+    auto rows = open_batch(rd, groups[t].root, groups[t].widths, tidx, groups[t].depth);
+    for (size_t q = 0; q < idx.size(); q++) {
+      const size_t k = std::lower_bound(tidx.begin(), tidx.end(), idx[q] & mask) - tidx.begin();
+      for (u64 v : rows[k]) reduced[q] = e2_add(e2_mul(reduced[q], alpha_d), e2_make(v));
+    }
+  }
+  const u64 wK = gl_two_adic_generator(L);
+  std::vector<std::pair<size_t, e2>> cur;  // (index in the current FRI domain, value)
+  for (size_t q = 0; q < idx.size(); q++) {
+    const e2 x = e2_make(gl_mul(g, gl_pow(wK, idx[q])));
+    e2 acc = e2_make(0), bp = e2_make(1);
+    for (int k = 0; k < n_points; k++) {
+      const e2 den = e2_sub(zs[k], x);
+      if (e2_is_zero(den)) throw Reject("out-of-domain point on the LDE coset");
+      acc = e2_add(acc, e2_mul(e2_mul(bp, e2_sub(fred[k], reduced[q])), e2_inv(den)));
+      bp = e2_mul(bp, beta_d);
+    }
+    cur.push_back({idx[q], acc});
+  }
+  // ---- FRI (fri/verifier.rs): each round's row must contain the running value and folds to the next one ----
+  int logn = L;
+  u64 gen_inv = gl_inv(gl_two_adic_generator(L));
+  const size_t arity = (size_t)1 << la;
+  for (int r = 0; r < rounds; r++) {
+    const int logf = logn - la;
+    const size_t mask = ((size_t)1 << logf) - 1;
+    std::vector<size_t> ridx;
+    for (auto& kv : cur) ridx.push_back(kv.first & mask);
+    std::sort(ridx.begin(), ridx.end());
+    ridx.erase(std::unique(ridx.begin(), ridx.end()), ridx.end());
+    auto rows = open_batch(rd, fri_roots[r], {arity * 2}, ridx, logf);
+    std::vector<std::pair<size_t, e2>> next;
+    for (auto& kv : cur) {
+      const size_t row = kv.first & mask;
+      const size_t pos = bitrev32((u32)(kv.first >> logf), la);
+      const size_t q = std::lower_bound(ridx.begin(), ridx.end(), row) - ridx.begin();
+      e2 y[8];
+      for (size_t k = 0; k < arity; k++) y[k] = e2{rows[q][2 * k], rows[q][2 * k + 1]};
+      if (!e2_eq(y[pos], kv.second)) throw Reject("FRI round " + std::to_string(r) + ": opened row disagrees with the folded value");
+      const e2 folded = fold_row(y, la, gl_pow(gen_inv, row), fri_betas[r]);
+      if (next.empty() || next.back().first != row) next.push_back({row, folded});
+      else if (!e2_eq(next.back().second, folded)) throw Reject("FRI: two queries fold to different values");
+    }
+    std::sort(next.begin(), next.end(), [](auto& a, auto& b) { return a.first < b.first; });
+    next.erase(std::unique(next.begin(), next.end(), [](auto& a, auto& b) { return a.first == b.first; }), next.end());
+    cur.swap(next);
+    logn = logf;
+    gen_inv = gl_exp_pow2(gen_inv, la);
+  }
+  {
+    const u64 gen = gl_two_adic_generator(logn);
+    for (auto& kv : cur) {
+      const u64 x = gl_pow(gen, kv.first);
+      e2 acc = e2_make(0);
+      for (e2 c : final_poly) acc = e2_add(e2_mulf(acc, x), c);
+      if (!e2_eq(acc, kv.second)) throw Reject("FRI: final polynomial mismatch");
+    }
+  }
+}
+
+void verify_impl(const mh_pcs_params& pp, const std::vector<DagIR>& airs, const std::vector<int>& lhs, const std::vector<u64>& publics,
+                 const u64* prep_root, Reader& rd, mh_external_assertions external, void* external_user, u64 digest[4]) {
+  const size_t n_airs = airs.size();
+  const int lb = pp.log_blowup;
+  check_params(pp);
   for (size_t i = 0; i < n_airs; i++) {
     if (lhs[i] < 1) throw Reject("trace too small");
     size_t pmax = 0;
@@ -350,104 +470,10 @@ void verify_impl(const mh_pcs_params& pp, const std::vector<DagIR>& airs, const 
   widths[g_main + 2].push_back(align8(2 * D));
   roots.push_back(main_root); roots.push_back(aux_root); roots.push_back(quot_root);
   for (int k = 0; k < 3; k++) depths.push_back(L);
-  size_t W = 0;
-  for (auto& ws : widths)
-    for (size_t w : ws) W += w;
+  std::vector<PcsGroup> groups;
+  for (size_t t = 0; t < widths.size(); t++) groups.push_back(PcsGroup{roots[t], widths[t], depths[t]});
   std::vector<e2> ev[2];
-  for (int k = 0; k < 2; k++)
-    for (size_t i = 0; i < W; i++) ev[k].push_back(rd.recv_ef());
-  rd.check_pow(pp.deep_pow_bits);
-  const e2 alpha_d = rd.ch.sample_ef(), beta_d = rd.ch.sample_ef();
-  e2 fred[2];
-  for (int k = 0; k < 2; k++) {
-    e2 a = e2_make(0);
-    for (size_t i = 0; i < W; i++) a = e2_add(e2_mul(a, alpha_d), ev[k][i]);
-    fred[k] = a;
-  }
-  const int rounds = fri_rounds(pp, L);
-  std::vector<Digest4> fri_roots;
-  std::vector<e2> fri_betas;
-  for (int r = 0; r < rounds; r++) {
-    fri_roots.push_back(rd.recv_digest());
-    rd.check_pow(pp.folding_pow_bits);
-    fri_betas.push_back(rd.ch.sample_ef());
-  }
-  const size_t fpd = (size_t)1 << std::max(0, L - rounds * la - lb);
-  std::vector<e2> final_poly;  // descending degree
-  for (size_t i = 0; i < fpd; i++) final_poly.push_back(rd.recv_ef());
-  rd.check_pow(pp.query_pow_bits);
-  std::vector<size_t> idx;
-  for (int i = 0; i < pp.num_queries; i++) idx.push_back(rd.ch.sample_bits(L));
-  std::sort(idx.begin(), idx.end());
-  idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
-
-  // ---- query phase: trace openings -> DEEP quotient values (deep/verifier.rs) ----
-  std::vector<e2> reduced(idx.size(), e2_make(0));
-  for (size_t t = 0; t < widths.size(); t++) {
-    // a tree shorter than the max domain is opened at the indices' low bits (lmcs/tree_indices.rs:72-84)
-    const size_t mask = ((size_t)1 << depths[t]) - 1;
-    std::vector<size_t> tidx;
-    for (size_t i : idx) tidx.push_back(i & mask);
-    std::sort(tidx.begin(), tidx.end());
-    tidx.erase(std::unique(tidx.begin(), tidx.end()), tidx.end());
-    auto rows = open_batch(rd, roots[t], widths[t], tidx, depths[t]);
-    for (size_t q = 0; q < idx.size(); q++) {
-      const size_t k = std::lower_bound(tidx.begin(), tidx.end(), idx[q] & mask) - tidx.begin();
-      for (u64 v : rows[k]) reduced[q] = e2_add(e2_mul(reduced[q], alpha_d), e2_make(v));
-    }
-  }
-  const u64 wK = gl_two_adic_generator(L);
-  std::vector<std::pair<size_t, e2>> cur;  // (index in the current FRI domain, value)
-  for (size_t q = 0; q < idx.size(); q++) {
-    const e2 x = e2_make(gl_mul(g, gl_pow(wK, idx[q])));
-    e2 acc = e2_make(0), bp = e2_make(1);
-    for (int k = 0; k < 2; k++) {
-      const e2 den = e2_sub(zs[k], x);
-      if (e2_is_zero(den)) throw Reject("out-of-domain point on the LDE coset");
-      acc = e2_add(acc, e2_mul(e2_mul(bp, e2_sub(fred[k], reduced[q])), e2_inv(den)));
-      bp = e2_mul(bp, beta_d);
-    }
-    cur.push_back({idx[q], acc});
-  }
-  // ---- FRI (fri/verifier.rs): each round's row must contain the running value and folds to the next one ----
-  int logn = L;
-  u64 gen_inv = gl_inv(gl_two_adic_generator(L));
-  const size_t arity = (size_t)1 << la;
-  for (int r = 0; r < rounds; r++) {
-    const int logf = logn - la;
-    const size_t mask = ((size_t)1 << logf) - 1;
-    std::vector<size_t> ridx;
-    for (auto& kv : cur) ridx.push_back(kv.first & mask);
-    std::sort(ridx.begin(), ridx.end());
-    ridx.erase(std::unique(ridx.begin(), ridx.end()), ridx.end());
-    auto rows = open_batch(rd, fri_roots[r], {arity * 2}, ridx, logf);
-    std::vector<std::pair<size_t, e2>> next;
-    for (auto& kv : cur) {
-      const size_t row = kv.first & mask;
-      const size_t pos = bitrev32((u32)(kv.first >> logf), la);
-      const size_t q = std::lower_bound(ridx.begin(), ridx.end(), row) - ridx.begin();
-      e2 y[8];
-      for (size_t k = 0; k < arity; k++) y[k] = e2{rows[q][2 * k], rows[q][2 * k + 1]};
-      if (!e2_eq(y[pos], kv.second)) throw Reject("FRI round " + std::to_string(r) + ": opened row disagrees with the folded value");
-      const e2 folded = fold_row(y, la, gl_pow(gen_inv, row), fri_betas[r]);
-      if (next.empty() || next.back().first != row) next.push_back({row, folded});
-      else if (!e2_eq(next.back().second, folded)) throw Reject("FRI: two queries fold to different values");
-    }
-    std::sort(next.begin(), next.end(), [](auto& a, auto& b) { return a.first < b.first; });
-    next.erase(std::unique(next.begin(), next.end(), [](auto& a, auto& b) { return a.first == b.first; }), next.end());
-    cur.swap(next);
-    logn = logf;
-    gen_inv = gl_exp_pow2(gen_inv, la);
-  }
-  {
-    const u64 gen = gl_two_adic_generator(logn);
-    for (auto& kv : cur) {
-      const u64 x = gl_pow(gen, kv.first);
-      e2 acc = e2_make(0);
-      for (e2 c : final_poly) acc = e2_add(e2_mulf(acc, x), c);
-      if (!e2_eq(acc, kv.second)) throw Reject("FRI: final polynomial mismatch");
-    }
-  }
+  pcs_verify_aligned(pp, L, groups, zs, 2, rd, ev);
   // ---- constraint identity at z (verifier/mod.rs): sum over AIRs (beta-folded) == Q(z) * Z_H(z) ----
   e2 accumulated = e2_make(0);
   size_t off_prep = 0, off_main = 0;
@@ -624,6 +650,105 @@ int mh_verify_hiding(int lmcs, int salt_elems, const mh_pcs_params* params, int 
   return verify_entry(lmcs, salt_elems, params, n_airs, air_blobs, air_blob_words, log_trace_heights, public_values, n_public_values,
                       challenger_state, pre_observe, n_pre_observe, fields, n_fields, commitments, n_commitments, preprocessed_root,
                       external, external_user, digest, err, err_cap);
+}
+// ---- the PCS on its own (pcs/verifier.rs:72-174) -------------------------------------------------------------------------------
+// domain.rs:539-553 for a caller-chosen point: nonzero, outside the trace domain H of the tallest matrix and outside the LDE coset gK.
+// Every shorter matrix is then safe too: its point z^L lies on its own H' or g'K' only if z lies on H or gK.
+static bool pcs_point_ok(int log_n, int lb, e2 z) {
+  if (e2_is_zero(z)) return false;
+  if (e2_eq(e2_exp_pow2(z, log_n), e2_make(1))) return false;
+  const u64 g_inv = gl_inv(gl_lde_shift(log_n + lb));
+  return !e2_eq(e2_exp_pow2(e2_mulf(z, g_inv), log_n + lb), e2_make(1));
+}
+int mh_pcs_point_ok(int log_max_trace_height, int log_blowup, const uint64_t z[2]) {
+  if (!z || log_max_trace_height < 0 || log_blowup < 0 || log_max_trace_height + log_blowup > 32) return 0;
+  return pcs_point_ok(log_max_trace_height, log_blowup, e2{gl_canon(z[0]), gl_canon(z[1])}) ? 1 : 0;
+}
+int mh_pcs_verify(int lmcs, int salt_elems, const mh_pcs_params* params, int n_trees, const uint64_t* roots, const uint8_t* log_tree_heights,
+                  const int* n_mats, const size_t* widths, int n_points, const uint64_t* points, const uint64_t challenger_state[12],
+                  const uint64_t* pre_observe, size_t n_pre_observe, const uint64_t* fields, size_t n_fields, const uint64_t* commitments,
+                  size_t n_commitments, uint64_t* evals_out, uint64_t digest[4], char* err, size_t err_cap) {
+  auto fail = [&](int code, const char* msg) {
+    if (err && err_cap) {
+      strncpy(err, msg, err_cap - 1);
+      err[err_cap - 1] = 0;
+    }
+    return code;
+  };
+  try {
+    MH_REQUIRE(params && roots && log_tree_heights && n_mats && widths && points && challenger_state && digest, "null argument");
+    MH_REQUIRE((pre_observe || !n_pre_observe) && (fields || !n_fields) && (commitments || !n_commitments), "null array");
+    MH_REQUIRE(n_trees >= 1 && n_trees <= 256, "need between 1 and 256 committed trees (pcs/verifier.rs:88 NoCommitments)");
+    MH_REQUIRE(n_points >= 1 && n_points <= MH_PCS_MAX_POINTS, "n_points must be in 1..MH_PCS_MAX_POINTS");
+    MH_REQUIRE(lmcs >= MH_LMCS_POSEIDON2 && lmcs <= MH_LMCS_RPX, "unknown LMCS hasher id");
+    MH_REQUIRE(salt_elems >= 0 && salt_elems <= MH_MAX_SALT_ELEMS, "salt_elems must be in 0..MH_MAX_SALT_ELEMS");
+    t_hash = lmcs;
+    t_salt = salt_elems;
+    check_params(*params);
+    const int lb = params->log_blowup;
+    int log_n = 0;
+    for (int t = 0; t < n_trees; t++) log_n = std::max(log_n, (int)log_tree_heights[t]);
+    const int L = log_n + lb;
+    if (L > 32) throw Reject("LDE order exceeds the field's two-adicity");
+    Reader rd;
+    rd.ch.hash = lmcs;
+    rd.ch.init_from_state(challenger_state);
+    for (size_t i = 0; i < n_pre_observe; i++) rd.ch.observe_framing(pre_observe[i]);
+    rd.f = fields; rd.nf = n_fields;
+    rd.c = commitments; rd.nc = n_commitments;
+    std::vector<PcsGroup> groups;
+    std::vector<size_t> raw;  // unpadded widths, flat
+    size_t wi = 0;
+    for (int t = 0; t < n_trees; t++) {
+      MH_REQUIRE(n_mats[t] >= 1 && n_mats[t] <= 4096, "every tree holds between 1 and 4096 matrices");
+      PcsGroup g;
+      for (int i = 0; i < 4; i++) {
+        g.root[i] = roots[4 * t + i];
+        if (!rd.ch.bytes() && g.root[i] >= GL_P) throw Reject("non-canonical digest element in a root");
+      }
+      for (int m = 0; m < n_mats[t]; m++) {
+        const size_t w = widths[wi++];
+        MH_REQUIRE(w <= ((size_t)1 << 20), "matrix width out of range");
+        raw.push_back(w);
+        g.widths.push_back(align8(w));
+      }
+      g.depth = (int)log_tree_heights[t] + lb;
+      groups.push_back(std::move(g));
+    }
+    e2 zs[MH_PCS_MAX_POINTS];
+    for (int k = 0; k < n_points; k++) {
+      zs[k] = e2{gl_canon(points[2 * k]), gl_canon(points[2 * k + 1])};
+      if (!pcs_point_ok(log_n, lb, zs[k])) throw Reject("evaluation point " + std::to_string(k) + " is zero, on the trace domain H or on the LDE coset gK");
+    }
+    size_t W = 0;
+    for (auto& g : groups)
+      for (size_t w : g.widths) W += w;
+    // every point's evaluations travel in `fields`: a shape wider than the stream is refused before anything is sized by it
+    if (W > n_fields / 2 / (size_t)n_points) throw Reject("transcript ran out of field elements: shorter than the evaluations of the declared shape");
+    std::vector<e2> ev[MH_PCS_MAX_POINTS];
+    pcs_verify_aligned(*params, L, groups, zs, n_points, rd, ev);
+    if (rd.pf != rd.nf || rd.pc != rd.nc) throw Reject("trailing data in the transcript");
+    rd.ch.finalize(digest);
+    if (evals_out) {  // verify_aligned's truncation (pcs/verifier.rs:156-171): the alignment padding is dropped
+      size_t o = 0;
+      for (int k = 0; k < n_points; k++) {
+        size_t a = 0;
+        for (size_t w : raw) {
+          for (size_t i = 0; i < w; i++) {
+            evals_out[o++] = ev[k][a + i].c0;
+            evals_out[o++] = ev[k][a + i].c1;
+          }
+          a += align8(w);
+        }
+      }
+    }
+    if (err && err_cap) err[0] = 0;
+    return MH_OK;
+  } catch (const MhError& e) {
+    return fail(e.code, e.what());
+  } catch (const std::exception& e) {
+    return fail(MH_ERR_INTERNAL, e.what());
+  }
 }
 // The cross-AIR assertion of a LogUp statement without boundary corrections: the committed accumulator finals
 // (aux value 0 of every instance that has one) sum to zero.
