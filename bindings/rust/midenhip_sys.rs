@@ -80,6 +80,55 @@ pub type mh_external_assertions = Option<
     unsafe extern "C" fn(user: *mut c_void, randomness: *const u64, n_randomness: usize, aux_values: *const *const u64, n_aux_values: *const usize, log_trace_heights: *const u8, n_airs: c_int, assertions_out: *mut u64, cap: usize) -> c_int,
 >;
 
+/// One LMCS batch opening as mh_tree_open wrote it (see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct mh_lmcs_opening {
+    pub root: [u64; 4],
+    pub log_height: c_int,
+    pub n_mats: c_int,
+    pub widths: *const usize,
+    pub alignment: usize,
+    pub indices: *const u64,
+    pub n_indices: usize,
+    pub fields: *const u64,
+    pub n_fields: usize,
+    pub commitments: *const u64,
+    pub n_commit_felts: usize,
+}
+/// What differs per proof of an mh_verify_batch call.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct mh_verify_item {
+    pub log_trace_heights: *const u8,
+    pub public_values: *const u64,
+    pub n_public_values: usize,
+    pub pre_observe: *const u64,
+    pub n_pre_observe: usize,
+    pub fields: *const u64,
+    pub n_fields: usize,
+    pub commitments: *const u64,
+    pub n_commitments: usize,
+    pub preprocessed_root: *const u64,
+    pub external_user: *mut c_void,
+}
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mh_verify_result {
+    pub code: c_int,
+    pub digest: [u64; 4],
+    pub reason: [c_char; 216],
+}
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct mh_miden_verify_item {
+    pub public_values: *const u64,
+    pub aux_inputs: *const u64,
+    pub n_aux_inputs: usize,
+    pub proof_bytes: *const u8,
+    pub n_bytes: usize,
+}
+
 /// Collectives of a sharded proof, on DEVICE buffers (RCCL): 0 = success.
 #[repr(C)]
 pub struct mh_comm {
@@ -277,6 +326,15 @@ unsafe extern "C" {
     pub fn mh_prove_miden(ctx: *mut mh_ctx, m: *const mh_miden, hash_fn: c_int, core_rowmajor: *const u64, log_core: c_int, chiplets_rowmajor: *const u64, log_chiplets: c_int, poseidon2_rowmajor: *const u64, log_poseidon2: c_int, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, out: *mut *mut mh_proof) -> c_int;
     pub fn mh_prove_miden_traces(ctx: *mut mh_ctx, m: *const mh_miden, hash_fn: c_int, traces: *const *mut mh_trace, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, out: *mut *mut mh_proof) -> c_int;
     pub fn mh_verify_miden(hash_fn: c_int, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, proof_bytes: *const u8, n_bytes: usize, digest: *mut u64, err: *mut c_char, err_cap: usize) -> c_int;
+    /// mh_verify_miden for n proofs through mh_verify_batch; results[i] as mh_verify_batch fills them
+    pub fn mh_verify_miden_batch(ctx: *mut mh_ctx, hash_fn: c_int, n: usize, items: *const mh_miden_verify_item, results: *mut mh_verify_result) -> c_int;
+    // ---- LMCS openings on their own (the counterpart of mh_tree_open) and the batch verifier ----
+    /// host only, no context
+    pub fn mh_lmcs_verify(lmcs: c_int, salt_elems: c_int, o: *const mh_lmcs_opening, err: *mut c_char, err_cap: usize) -> c_int;
+    /// the same for n openings on the device; ok[i] = 1 iff mh_lmcs_verify accepts items[i]
+    pub fn mh_lmcs_verify_batch(ctx: *mut mh_ctx, lmcs: c_int, salt_elems: c_int, n: usize, items: *const mh_lmcs_opening, ok: *mut c_int) -> c_int;
+    /// mh_verify_hiding for many proofs of one statement shape: host replay per item, every opening hashed on the device
+    pub fn mh_verify_batch(ctx: *mut mh_ctx, lmcs: c_int, salt_elems: c_int, params: *const mh_pcs_params, n_airs: c_int, air_blobs: *const *const u64, air_blob_words: *const usize, challenger_state: *const u64, external: mh_external_assertions, n_items: usize, items: *const mh_verify_item, results: *mut mh_verify_result) -> c_int;
     pub fn mh_miden_pcs_params(out: *mut mh_pcs_params);
     pub fn mh_miden_challenger_state(state: *mut u64);
     pub fn mh_miden_hash_kernel_digests(kernel_felts: *const u64, n_felts: usize, out: *mut u64) -> c_int;

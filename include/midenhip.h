@@ -560,6 +560,78 @@ int mh_external_precompile_session_ec_only(void* user, const uint64_t* randomnes
                                            const size_t* n_aux_values, const uint8_t* log_trace_heights, int n_airs,
                                            uint64_t* assertions_out, size_t cap);
 
+/* ---- LMCS openings checked on their own, and the batch verifier --------------------------------------------------------------------
+ * mh_lmcs_verify is the counterpart of mh_tree_open (the reference's Lmcs::open_batch, lmcs/config.rs:172-211): HOST ONLY, no context.
+ * An opening = the root, the tree's log height (= depth: log2 of its leaves, the LDE height), the UNALIGNED widths of its matrices in
+ * commitment order, the row alignment the opening was made with, the opened indices (any order, duplicates allowed, as mh_tree_open
+ * takes them) and the two streams exactly as mh_tree_open wrote them.  salt_elems = mh_tree_salt_elems of the tree.
+ * MH_OK, or MH_ERR_INVALID + a reason in err (may be NULL): a stream too short or with trailing data, a non-canonical felt (under the
+ * byte-hash configurations a digest word is not a felt and is not checked), an index outside the tree, an unknown lmcs, salt outside
+ * 0..MH_MAX_SALT_ELEMS, no index, more than 4096 matrices, a width or alignment above 2^20, or "Merkle root mismatch". */
+typedef struct mh_lmcs_opening {
+  uint64_t root[4];
+  int log_height;
+  int n_mats;
+  const size_t* widths; /* [n_mats], unaligned */
+  size_t alignment;     /* 8 / 17 (Keccak) / 1 (Blake3) for a proof's trees; whatever mh_tree_open was given otherwise */
+  const uint64_t* indices;
+  size_t n_indices;
+  const uint64_t* fields; /* per sorted unique index: every matrix's aligned row, then the salt */
+  size_t n_fields;
+  const uint64_t* commitments; /* the sibling digests that cannot be derived, bottom-up, left to right; 4 words each */
+  size_t n_commit_felts;
+} mh_lmcs_opening;
+int mh_lmcs_verify(int lmcs, int salt_elems, const mh_lmcs_opening* o, char* err, size_t err_cap);
+/* The same for n openings on the DEVICE: every leaf of every opening is hashed by one kernel (one lane per leaf, leaves of one shape
+ * per wave), every path by a second one (one workgroup per opening, the levels in LDS) -- a constant number of launches per batch,
+ * one read-back.  ok[i] = 1 iff mh_lmcs_verify accepts items[i]; an opening the host checks refuse (lengths, indices, felts) gets 0
+ * without reaching the device.  Device memory per pass is bounded by the environment variable MH_VERIFY_BATCH_BYTES (default 256 MB):
+ * a larger batch runs as consecutive chunks.  Call-level failures only in the return value: null arguments, a HIP error, and
+ * MH_ERR_INVALID for an opening of more than 1024 distinct leaves or a matrix wider than 32764 cells (the kernels' bounds: use the
+ * host call for those); the reason is mh_last_error's.  n = 0 is MH_OK. */
+int mh_lmcs_verify_batch(mh_ctx* ctx, int lmcs, int salt_elems, size_t n, const mh_lmcs_opening* items, int* ok);
+
+/* mh_verify_hiding for MANY proofs of one statement shape: the AIR list, the parameters, the challenger state and the external
+ * assertions are the batch's, an item carries what differs per proof.  For a node that sits beside the provers and accepts many
+ * proofs before it aggregates them; a verifier box without a GPU keeps mh_verify*.  Each item is replayed on the host (transcript,
+ * constraint identity, DEEP and FRI algebra, proof of work: up to 16 threads, so `external` is called from several threads at once,
+ * each call with its item's external_user) while its LMCS openings are only recorded; then ONE device pass hashes every recorded
+ * opening of every item (the two kernels of mh_lmcs_verify_batch).  A replay that fails keeps the openings it recorded before the
+ * failure, because they come earlier in the proof: a damaged opened row fails its tree's root in mh_verify_hiding, and fails the
+ * algebra behind the opening only here, where the hashing is postponed.
+ * Verdict: results[i].code = MH_OK iff the replay succeeded and all openings verified, else MH_ERR_INVALID; accept / reject equals
+ * mh_verify_hiding's on the same item in every case, and an accepted item's digest is its digest.  The REASON: a failed opening
+ * reads "proof rejected: Merkle root mismatch (<tree>)" with <tree> = "committed tree t of n" in the order [preprocessed?, main,
+ * aux, quotient] or "FRI round r tree", the first failed one of the item; otherwise the replay's reason stands.  It is
+ * mh_verify_hiding's reason (plus the tree) except for a proof with more than one defect, where an opening recorded before the
+ * replay's failure wins even if mh_verify_hiding meets another defect first.  An item with more than 1024 distinct query indices is rejected with
+ * a reason (the path kernel's bound).  The return value is for call-level failures only (null arguments, malformed AIR blobs, a HIP
+ * error); n_items = 0 is MH_OK.  When to prefer the host call: measured on the Miden statement of a 2^16-row program (DESIGN.md
+ * section 3j), a single proof gains 0.3 ms of 1.7 under Poseidon2 and nothing under Blake3 (0.37 against 0.39 ms); from 8 proofs on
+ * the batch is 3 to 20 times faster per proof, under Blake3 through the replay threads rather than the device.
+ * Not there yet: batch forms of mh_verify_precompile and mh_pcs_verify (they go through the same recorded openings), sharded contexts. */
+typedef struct mh_verify_item {
+  const uint8_t* log_trace_heights; /* [n_airs], instance order */
+  const uint64_t* public_values;
+  size_t n_public_values;
+  const uint64_t* pre_observe;
+  size_t n_pre_observe;
+  const uint64_t* fields;
+  size_t n_fields;
+  const uint64_t* commitments;
+  size_t n_commitments;              /* digests */
+  const uint64_t* preprocessed_root; /* [4] or NULL */
+  void* external_user;
+} mh_verify_item;
+typedef struct mh_verify_result {
+  int code; /* MH_OK or MH_ERR_INVALID */
+  uint64_t digest[4];
+  char reason[216]; /* "" when accepted */
+} mh_verify_result;
+int mh_verify_batch(mh_ctx* ctx, int lmcs, int salt_elems, const mh_pcs_params* params, int n_airs, const uint64_t* const* air_blobs,
+                    const size_t* air_blob_words, const uint64_t challenger_state[12], mh_external_assertions external, size_t n_items,
+                    const mh_verify_item* items, mh_verify_result* results);
+
 /* ---- the precompile prover's session: SessionTraces::prove_stark's own shape (precompiles-prover/src/session/prove.rs:295-330, 385-416)
  * Twelve main traces + the transcript root in, proof out -- the statement layer `ChipletMultiAir` adds to the proof system, in the
  * library (csrc/precompile.cpp) so that a C caller restates nothing:
@@ -633,6 +705,16 @@ int mh_prove_miden_traces(mh_ctx* ctx, const mh_miden* m, int hash_fn, mh_trace*
  * Host only (no context, no GPU). */
 int mh_verify_miden(int hash_fn, const uint64_t* public_values /* [32] */, const uint64_t* aux_inputs, size_t n_aux_inputs,
                     const uint8_t* proof_bytes, size_t n_bytes, uint64_t digest[4], char* err, size_t err_cap);
+/* mh_verify_miden for n proofs through mh_verify_batch: per proof the arguments of mh_verify_miden; results[i] as mh_verify_batch
+ * fills them (accept / reject and digest = mh_verify_miden's).  Malformed bytes or inputs reject that item alone. */
+typedef struct mh_miden_verify_item {
+  const uint64_t* public_values; /* [32] */
+  const uint64_t* aux_inputs;
+  size_t n_aux_inputs;
+  const uint8_t* proof_bytes;
+  size_t n_bytes;
+} mh_miden_verify_item;
+int mh_verify_miden_batch(mh_ctx* ctx, int hash_fn, size_t n, const mh_miden_verify_item* items, mh_verify_result* results);
 /* the pieces, for a caller that drives mh_prove / mh_session_* / mh_verify_ex itself */
 void mh_miden_pcs_params(mh_pcs_params* out);
 void mh_miden_challenger_state(uint64_t state[12]);

@@ -43,6 +43,7 @@ EXPORTS = [
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
     "mh_pcs_fri_fold", "mh_pcs_fri_final", "mh_pcs_query", "mh_pcs_open", "mh_pcs_verify", "mh_session_trees",
+    "mh_lmcs_verify", "mh_lmcs_verify_batch", "mh_verify_batch", "mh_verify_miden_batch",
 ]
 
 MH_MAX_SALT_ELEMS = 8  # mh_ctx_set_salt: the largest salt width of the hiding LMCS
@@ -491,6 +492,15 @@ class LmcsTree:
         self.ctx.check(self.ctx.lib.mh_tree_open(self.ctx.h, self.h, _ptr(idx), C.c_size_t(n), C.c_size_t(alignment),
                                                  _ptr(fields), C.byref(nf), _ptr(commits), C.byref(nc)))
         return fields[:nf.value].copy(), commits[:nc.value].reshape(-1, 4).copy()
+
+    def opening(self, indices, fields, commitments, alignment=8):
+        """The mh_lmcs_opening of what prove_batch(indices, alignment) returned, against this tree's root."""
+        return LmcsOpening.make(self.root(), self.log_height, self.widths, alignment, indices, fields, commitments)
+
+    def verify_open(self, indices, fields, commitments, alignment=8):
+        """mh_lmcs_verify (host only) of an opening of this tree: (True, "") or (False, reason)."""
+        lmcs = {v: k for k, v in Ctx.LMCS.items()}[self.ctx.lib.mh_ctx_get_lmcs(self.ctx.h)]
+        return lmcs_verify(self.opening(indices, fields, commitments, alignment), lmcs, self.salt_elems)
 
     def download_lde(self, mat):
         rows = 1 << (self.log_heights[mat] + self.log_blowup)
@@ -1094,6 +1104,106 @@ def verify(airs, log_trace_heights, public_values, params, challenger_state, pre
     return (True, digest) if rc == 0 else (False, err.value.decode())
 
 
+# ---- LMCS openings on their own and the batch verifier (csrc/lmcs_verify.cpp, csrc/verify_batch.hip) ---------------------------------
+class LmcsOpening(C.Structure):
+    """mh_lmcs_opening; make() keeps the arrays it points to alive."""
+    _fields_ = [("root", C.c_uint64 * 4), ("log_height", C.c_int), ("n_mats", C.c_int), ("widths", C.POINTER(C.c_size_t)),
+                ("alignment", C.c_size_t), ("indices", u64p), ("n_indices", C.c_size_t), ("fields", u64p), ("n_fields", C.c_size_t),
+                ("commitments", u64p), ("n_commit_felts", C.c_size_t)]
+
+    @classmethod
+    def make(cls, root, log_height, widths, alignment, indices, fields, commitments):
+        o = cls()
+        w = (C.c_size_t * max(1, len(widths)))(*[int(x) for x in widths])
+        idx, f = _arr([int(i) for i in indices]), _arr(fields)
+        c = _arr(np.asarray(commitments, dtype=np.uint64).reshape(-1))
+        o._keep = (w, idx, f, c)
+        o.root = (C.c_uint64 * 4)(*[int(x) for x in root])
+        o.log_height, o.n_mats, o.widths, o.alignment = int(log_height), len(widths), w, int(alignment)
+        o.indices, o.n_indices = (_ptr(idx) if idx.size else None), idx.size
+        o.fields, o.n_fields = (_ptr(f) if f.size else None), f.size
+        o.commitments, o.n_commit_felts = (_ptr(c) if c.size else None), c.size
+        return o
+
+
+def _openings(openings):
+    items = [o if isinstance(o, LmcsOpening) else LmcsOpening.make(**o) for o in openings]
+    arr = (LmcsOpening * max(1, len(items)))(*items)
+    return items, arr
+
+
+def lmcs_verify(opening, lmcs="poseidon2", salt_elems=0):
+    """mh_lmcs_verify (host only): opening = an LmcsOpening or the keyword arguments of LmcsOpening.make as a dict.
+    Returns (True, "") or (False, reason)."""
+    lib = load_library()
+    items, arr = _openings([opening])
+    err = C.create_string_buffer(512)
+    lib.mh_lmcs_verify.argtypes = [C.c_int, C.c_int, C.POINTER(LmcsOpening), C.c_char_p, C.c_size_t]
+    rc = lib.mh_lmcs_verify(Ctx.LMCS[lmcs], int(salt_elems), arr, err, 512)
+    return (rc == 0, err.value.decode())
+
+
+def lmcs_verify_batch(ctx, openings, lmcs="poseidon2", salt_elems=0):
+    """mh_lmcs_verify_batch: the openings hashed on the device; returns the list of 0/1 verdicts."""
+    items, arr = _openings(openings)
+    ok = (C.c_int * max(1, len(items)))()
+    ctx.lib.mh_lmcs_verify_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(LmcsOpening), C.POINTER(C.c_int)]
+    ctx.check(ctx.lib.mh_lmcs_verify_batch(ctx.h, Ctx.LMCS[lmcs], int(salt_elems), len(items), arr, ok))
+    return [int(ok[i]) for i in range(len(items))]
+
+
+class VerifyItem(C.Structure):
+    _fields_ = [("log_trace_heights", C.POINTER(C.c_uint8)), ("public_values", u64p), ("n_public_values", C.c_size_t),
+                ("pre_observe", u64p), ("n_pre_observe", C.c_size_t), ("fields", u64p), ("n_fields", C.c_size_t),
+                ("commitments", u64p), ("n_commitments", C.c_size_t), ("preprocessed_root", u64p), ("external_user", C.c_void_p)]
+
+
+class VerifyResult(C.Structure):
+    _fields_ = [("code", C.c_int), ("digest", C.c_uint64 * 4), ("reason", C.c_char * 216)]
+
+
+def _results(res, n):
+    return [(True, np.array(list(res[i].digest), dtype=np.uint64)) if res[i].code == 0 else (False, res[i].reason.decode()) for i in range(n)]
+
+
+def verify_batch(ctx, airs, items, params, challenger_state, external=None, lmcs="poseidon2", salt_elems=0):
+    """mh_verify_batch: many proofs of one statement shape -- host replay per item, every LMCS opening of the batch hashed on the
+    device.  items = dicts with log_trace_heights, public_values, pre_observe, fields, commitments and optionally
+    preprocessed_root; external as in verify().  Returns per item what verify() returns: (True, digest) or (False, reason)."""
+    lib = ctx.lib
+    n = len(airs)
+    blobs = [_arr(a.blob) for a in airs]
+    bp = (u64p * n)(*[_ptr(b) for b in blobs])
+    bl = (C.c_size_t * n)(*[b.size for b in blobs])
+    p = params if isinstance(params, PcsParams) else PcsParams.from_dict(params)
+    st = _arr(challenger_state)
+    if external in ("precompile_session", "precompile_session_ec_only"):
+        external = C.cast(lib.mh_external_precompile_session_ec_only if external.endswith("ec_only") else lib.mh_external_precompile_session, EXTERNAL_FN)
+    elif external == "logup_balance":
+        external = C.cast(lib.mh_external_logup_balance, EXTERNAL_FN)
+    arr = (VerifyItem * max(1, len(items)))()
+    keep = []
+    for k, it in enumerate(items):
+        lh = (C.c_uint8 * n)(*[int(x) for x in it["log_trace_heights"]])
+        pub, pre = _arr(list(it.get("public_values", ())) or [0]), _arr(list(it.get("pre_observe", ())) or [0])
+        f, c = _arr(it["fields"]), _arr(np.asarray(it["commitments"], dtype=np.uint64).reshape(-1))
+        proot = _arr(it["preprocessed_root"]) if it.get("preprocessed_root") is not None else None
+        keep.append((lh, pub, pre, f, c, proot))
+        arr[k].log_trace_heights = lh
+        arr[k].public_values, arr[k].n_public_values = _ptr(pub), len(it.get("public_values", ()))
+        arr[k].pre_observe, arr[k].n_pre_observe = _ptr(pre), len(it.get("pre_observe", ()))
+        arr[k].fields, arr[k].n_fields = (_ptr(f) if f.size else None), f.size
+        arr[k].commitments, arr[k].n_commitments = (_ptr(c) if c.size else None), c.size // 4
+        arr[k].preprocessed_root = _ptr(proot) if proot is not None else None
+        arr[k].external_user = None
+    res = (VerifyResult * max(1, len(items)))()
+    lib.mh_verify_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(PcsParams), C.c_int, C.POINTER(u64p), C.POINTER(C.c_size_t), u64p,
+                                    EXTERNAL_FN, C.c_size_t, C.POINTER(VerifyItem), C.POINTER(VerifyResult)]
+    ctx.check(lib.mh_verify_batch(ctx.h, Ctx.LMCS[lmcs], int(salt_elems), C.byref(p), n, bp, bl, _ptr(st),
+                                  external if external is not None else C.cast(None, EXTERNAL_FN), len(items), arr, res))
+    return _results(res, len(items))
+
+
 # ---- the Miden VM statement in the library (csrc/miden.cpp): prove_stark's own shape, prover/src/lib.rs:317-355 ---------------------
 class Miden:
     """mh_miden_load: the three AIRs of `MidenMultiAir` with their lookup programs on a context.  prove(core, chiplets, poseidon2,
@@ -1184,6 +1294,27 @@ def verify_miden(public_values, aux_inputs, proof_bytes, hash_fn="poseidon2"):
     lib.mh_verify_miden.argtypes = [C.c_int, u64p, u64p, C.c_size_t, C.c_void_p, C.c_size_t, u64p, C.c_char_p, C.c_size_t]
     rc = lib.mh_verify_miden(Ctx.LMCS[hash_fn], _ptr(pv), _ptr(aux), len(aux_inputs), buf, len(proof_bytes), _ptr(digest), err, 512)
     return (True, digest) if rc == 0 else (False, err.value.decode())
+
+
+class MidenVerifyItem(C.Structure):
+    _fields_ = [("public_values", u64p), ("aux_inputs", u64p), ("n_aux_inputs", C.c_size_t), ("proof_bytes", C.c_void_p), ("n_bytes", C.c_size_t)]
+
+
+def verify_miden_batch(ctx, items, hash_fn="poseidon2"):
+    """mh_verify_miden_batch: items = (public_values, aux_inputs, proof_bytes) per proof; per item what verify_miden returns."""
+    n = len(items)
+    arr = (MidenVerifyItem * max(1, n))()
+    keep = []
+    for k, (public_values, aux_inputs, proof_bytes) in enumerate(items):
+        pv, aux = _arr([int(x) for x in public_values]), _arr([int(x) for x in aux_inputs] or [0])
+        buf = (C.c_uint8 * max(1, len(proof_bytes))).from_buffer_copy(bytes(proof_bytes) or b"\0")
+        keep.append((pv, aux, buf))
+        arr[k].public_values, arr[k].aux_inputs, arr[k].n_aux_inputs = _ptr(pv), _ptr(aux), len(aux_inputs)
+        arr[k].proof_bytes, arr[k].n_bytes = C.cast(buf, C.c_void_p), len(proof_bytes)
+    res = (VerifyResult * max(1, n))()
+    ctx.lib.mh_verify_miden_batch.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(MidenVerifyItem), C.POINTER(VerifyResult)]
+    ctx.check(ctx.lib.mh_verify_miden_batch(ctx.h, Ctx.LMCS[hash_fn], n, arr, res))
+    return _results(res, n)
 
 
 class Precompile:

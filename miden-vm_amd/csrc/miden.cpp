@@ -303,6 +303,71 @@ int mh_verify_miden(int hash_fn, const uint64_t* public_values, const uint64_t* 
                         mh_proof_num_commitments(p), nullptr, external_cb, &st, digest, err, err_cap);
 }
 
+// mh_verify_miden for n proofs through mh_verify_batch (verify_batch.hip): the statement layer per item exactly as above, the openings of
+// all of them hashed on the device in one pass.  An item mh_verify_miden refuses before it reads the proof is refused here the same way.
+int mh_verify_miden_batch(mh_ctx* ctx, int hash_fn, size_t n, const mh_miden_verify_item* items, mh_verify_result* results) {
+  if (!ctx) return MH_ERR_INVALID;
+  if (n && (!items || !results)) {
+    ctx->err = "mh_verify_miden_batch: null argument";
+    return MH_ERR_INVALID;
+  }
+  if (!n) return MH_OK;
+  mh_pcs_params prm;
+  mh_miden_pcs_params(&prm);
+  u64 state[12];
+  mh_miden_challenger_state(state);
+  struct Held {
+    u64 pre[MH_MIDEN_PRE_OBSERVE_FELTS];
+    Statement st;
+    std::unique_ptr<mh_proof, void (*)(mh_proof*)> proof{nullptr, mh_proof_free};
+  };
+  std::vector<Held> held(n);
+  std::vector<mh_verify_item> batch;
+  std::vector<size_t> who;
+  auto refuse = [&](size_t i, const char* msg) {
+    results[i].code = MH_ERR_INVALID;
+    memset(results[i].digest, 0, sizeof results[i].digest);
+    snprintf(results[i].reason, sizeof results[i].reason, "%s", msg);
+  };
+  for (size_t i = 0; i < n; i++) {
+    const mh_miden_verify_item& it = items[i];
+    Held& h = held[i];
+    if (!it.proof_bytes) { refuse(i, "null argument"); continue; }
+    if (mh_miden_pre_observe(&prm, it.public_values, it.aux_inputs, it.n_aux_inputs, h.pre) != MH_OK) {
+      refuse(i, "malformed public values / aux inputs");
+      continue;
+    }
+    mh_proof* p = nullptr;
+    if (mh_proof_deserialize(it.proof_bytes, it.n_bytes, &p) != MH_OK) { refuse(i, "malformed proof bytes"); continue; }
+    h.proof.reset(p);
+    if (mh_proof_num_traces(p) != 3) { refuse(i, "a Miden proof has three traces"); continue; }
+    h.st = Statement{it.aux_inputs, it.n_aux_inputs};
+    mh_verify_item v{};
+    v.log_trace_heights = mh_proof_log_trace_heights(p);
+    v.public_values = it.public_values;
+    v.n_public_values = NUM_PUBLIC;
+    v.pre_observe = h.pre;
+    v.n_pre_observe = MH_MIDEN_PRE_OBSERVE_FELTS;
+    v.fields = mh_proof_fields(p);
+    v.n_fields = mh_proof_num_fields(p);
+    v.commitments = mh_proof_commitments(p);
+    v.n_commitments = mh_proof_num_commitments(p);
+    v.preprocessed_root = nullptr;
+    v.external_user = &h.st;
+    batch.push_back(v);
+    who.push_back(i);
+  }
+  if (batch.empty()) return MH_OK;
+  const Blobs& b = blobs();
+  const uint64_t* blob_ptr[3] = {b.dag[0].data(), b.dag[1].data(), b.dag[2].data()};
+  const size_t blob_len[3] = {b.dag[0].size(), b.dag[1].size(), b.dag[2].size()};
+  std::vector<mh_verify_result> out(batch.size());
+  const int rc = mh_verify_batch(ctx, hash_fn, 0, &prm, 3, blob_ptr, blob_len, state, external_cb, batch.size(), batch.data(), out.data());
+  if (rc != MH_OK) return rc;
+  for (size_t k = 0; k < batch.size(); k++) results[who[k]] = out[k];
+  return MH_OK;
+}
+
 // ExecutionTrace::check_constraints (processor/src/trace/mod.rs:261-278) of this statement: check.hip with the statement's challenger state,
 // pre-observe schedule and eval_external
 static int check_common(mh_ctx* ctx, const mh_miden* m, mh_trace* const* traces, const uint64_t* public_values, const uint64_t* aux_inputs,

@@ -13,6 +13,7 @@
 #include "gl.cuh"
 #include "kernels.hpp"
 #include "lmcs_host.hpp"
+#include "lmcs_verify.hpp"
 #include <algorithm>
 #include <cstring>
 #include <numeric>
@@ -71,6 +72,14 @@ struct Reader {
 thread_local int t_hash = 0;
 // hiding LMCS (mh_verify_hiding): salt felts hinted after every opened leaf's rows, absorbed last; 0 = the plain LMCS
 thread_local int t_salt = 0;
+// mh_verify_batch (verify_batch.hip): while set, open_batch RECORDS every opening -- its plan, its root and where its rows and siblings
+// lie in the proof's streams -- instead of hashing it; the batch hashes all of them on the device afterwards.  Null for every other entry.
+struct OpeningSink {
+  std::vector<lmcs_plan::Opening>* openings;
+  std::vector<std::string>* labels;
+  std::string label;  // the tree the next open_batch belongs to
+};
+thread_local OpeningSink* t_sink = nullptr;
 // aligned_len(w, lmcs.alignment()) (util/align.rs:7-13, proof.rs:268): the sponge's rate -- 8, or 17 for Keccak -- and 1 for the
 // chaining hasher of the Blake3 LMCS.  (The name dates from the Poseidon2 configuration.)
 size_t align8(size_t w) {
@@ -149,8 +158,26 @@ std::vector<std::vector<u64>> open_batch(Reader& rd, const Digest4& root, const 
   if (t_salt) hashed.push_back((size_t)t_salt);
   std::vector<std::vector<u64>> rows(idx.size(), std::vector<u64>(total + (size_t)t_salt));
   std::vector<std::pair<size_t, Digest4>> level;
+  const u64* rows_at = rd.f + rd.pf;
   for (size_t q = 0; q < idx.size(); q++)
     for (auto& x : rows[q]) x = rd.hint_field();
+  if (t_sink) {  // the same reads and the same checks of the streams; the digests are left to the batch
+    lmcs_plan::Opening op;
+    std::string why;
+    const std::vector<uint64_t> idx64(idx.begin(), idx.end());
+    if (!lmcs_plan::build(depth, idx64.data(), idx64.size(), op.plan, why)) throw Reject(why);
+    op.sibs = rd.c + 4 * rd.pc;
+    for (size_t s = 0; s < op.plan.n_siblings; s++) (void)rd.hint_digest();
+    op.rows = rows_at;
+    op.row_len = total + (size_t)t_salt;
+    for (size_t w : hashed) op.hashed.push_back((uint32_t)w);
+    for (int i = 0; i < 4; i++) op.root[i] = root[i];
+    t_sink->openings->push_back(std::move(op));
+    t_sink->labels->push_back(t_sink->label);
+    if (t_salt)
+      for (auto& r : rows) r.resize(total);
+    return rows;
+  }
   {
     const std::vector<Digest4> leaves = leaf_digests(rows, hashed);
     for (size_t q = 0; q < idx.size(); q++) level.push_back({idx[q], leaves[q]});
@@ -336,6 +363,7 @@ void pcs_verify_aligned(const mh_pcs_params& pp, int L, const std::vector<PcsGro
     for (size_t i : idx) tidx.push_back(i & mask);
     std::sort(tidx.begin(), tidx.end());
     tidx.erase(std::unique(tidx.begin(), tidx.end()), tidx.end());
+    if (t_sink) t_sink->label = "committed tree " + std::to_string(t) + " of " + std::to_string(groups.size());
     auto rows = open_batch(rd, groups[t].root, groups[t].widths, tidx, groups[t].depth);
     for (size_t q = 0; q < idx.size(); q++) {
       const size_t k = std::lower_bound(tidx.begin(), tidx.end(), idx[q] & mask) - tidx.begin();
@@ -366,6 +394,7 @@ void pcs_verify_aligned(const mh_pcs_params& pp, int L, const std::vector<PcsGro
     for (auto& kv : cur) ridx.push_back(kv.first & mask);
     std::sort(ridx.begin(), ridx.end());
     ridx.erase(std::unique(ridx.begin(), ridx.end()), ridx.end());
+    if (t_sink) t_sink->label = "FRI round " + std::to_string(r) + " tree";
     auto rows = open_batch(rd, fri_roots[r], {arity * 2}, ridx, logf);
     std::vector<std::pair<size_t, e2>> next;
     for (auto& kv : cur) {
@@ -610,6 +639,46 @@ static int verify_entry(int lmcs, int salt_elems, const mh_pcs_params* params, i
     return fail(e.code, e.what());
   } catch (const std::exception& e) {
     return fail(MH_ERR_INTERNAL, e.what());
+  }
+}
+
+// One item of mh_verify_batch: verify_entry's replay with the sink set -- the transcript, the algebra and the proof-of-work checks
+// run here, the openings are recorded for the device.  Called from several threads at once (t_hash, t_salt and t_sink are per thread).
+int verify_replay_recording(int lmcs, int salt_elems, const mh_pcs_params& params, const std::vector<DagIR>& airs, const uint64_t challenger_state[12],
+                            mh_external_assertions external, const mh_verify_item& it, std::vector<lmcs_plan::Opening>& openings,
+                            std::vector<std::string>& labels, uint64_t digest[4], std::string& reason) {
+  OpeningSink sink{&openings, &labels, std::string()};
+  struct Unset {
+    ~Unset() { t_sink = nullptr; }
+  } unset;
+  try {
+    MH_REQUIRE(it.log_trace_heights, "null log_trace_heights");
+    MH_REQUIRE((it.public_values || !it.n_public_values) && (it.pre_observe || !it.n_pre_observe) && (it.fields || !it.n_fields) &&
+                   (it.commitments || !it.n_commitments),
+               "null array");
+    std::vector<int> lhs;
+    for (size_t i = 0; i < airs.size(); i++) lhs.push_back(it.log_trace_heights[i]);
+    t_hash = lmcs;
+    t_salt = salt_elems;
+    t_sink = &sink;
+    Reader rd;
+    rd.ch.hash = lmcs;
+    rd.ch.init_from_state(challenger_state);
+    for (size_t i = 0; i < it.n_pre_observe; i++) rd.ch.observe_framing(it.pre_observe[i]);
+    rd.f = it.fields; rd.nf = it.n_fields;
+    rd.c = it.commitments; rd.nc = it.n_commitments;
+    u64 proot[4];
+    if (it.preprocessed_root)
+      for (int i = 0; i < 4; i++) proot[i] = rd.ch.bytes() ? it.preprocessed_root[i] : gl_canon(it.preprocessed_root[i]);
+    verify_impl(params, airs, lhs, std::vector<u64>(it.public_values, it.public_values + it.n_public_values),
+                it.preprocessed_root ? proot : nullptr, rd, external, it.external_user, digest);
+    return MH_OK;
+  } catch (const MhError& e) {
+    reason = e.what();
+    return e.code;
+  } catch (const std::exception& e) {
+    reason = e.what();
+    return MH_ERR_INTERNAL;
   }
 }
 
