@@ -352,6 +352,7 @@ unsafe extern "C" {
     pub fn mh_proof_serialize(p: *const mh_proof, out: *mut u8, cap: usize) -> usize;
     // ---- constraint checker (ExecutionTrace::check_constraints, SessionTraces::check): MH_OK or MH_ERR_UNSATISFIED + the entries
     pub fn mh_check_constraints(ctx: *mut mh_ctx, air: *const mh_air, main_trace: *const mh_trace, aux: *const mh_trace, preprocessed: *const mh_trace, public_values: *const u64, n_public: usize, randomness: *const u64, n_randomness: usize, aux_values: *const u64, n_aux_values: usize, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize, failing_rows: *mut u64) -> c_int;
+    pub fn mh_constraint_fold(ctx: *mut mh_ctx, air: *const mh_air, main_trace: *const mh_trace, aux: *const mh_trace, preprocessed: *const mh_trace, public_values: *const u64, n_public: usize, randomness: *const u64, n_randomness: usize, aux_values: *const u64, n_aux_values: usize, alpha: *const u64, out: *mut u64) -> c_int;
     pub fn mh_check_miden(ctx: *mut mh_ctx, m: *const mh_miden, core_rowmajor: *const u64, log_core: c_int, chiplets_rowmajor: *const u64, log_chiplets: c_int, poseidon2_rowmajor: *const u64, log_poseidon2: c_int, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize) -> c_int;
     pub fn mh_check_miden_traces(ctx: *mut mh_ctx, m: *const mh_miden, traces: *const *mut mh_trace, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize) -> c_int;
     pub fn mh_check_precompile(ctx: *mut mh_ctx, s: *mut mh_precompile, mains_rowmajor: *const *const u64, log_heights: *const c_int, public_root: *const u64, flags: c_int, out: *mut mh_check_entry, cap: usize, n_entries: *mut usize) -> c_int;

@@ -769,6 +769,15 @@ int mh_check_constraints(mh_ctx* ctx, const mh_air* air, const mh_trace* main_tr
                          const mh_trace* preprocessed /* or NULL */, const uint64_t* public_values, size_t n_public,
                          const uint64_t* randomness /* EF pairs */, size_t n_randomness, const uint64_t* aux_values /* EF pairs */,
                          size_t n_aux_values, int flags, mh_check_entry* out, size_t cap, size_t* n_entries, uint64_t* failing_rows);
+/* Test and diagnostic entry, like mh_pcs_download_deep: the screen's fold itself, with the caller's alpha instead of a fresh random one.
+ * out [2^log_n][2] receives F(r) = sum_k alpha^(K-1-k) C_k(r) as canonical EF pairs, one per row, computed by the AIR's own constraint
+ * program (compiled chunks or interpreter, whichever mh_air_load chose) on the trace domain with the screen's selector values:
+ * is_first = [r == 0], is_last = [r == n-1], is_transition = w_n^r - w_n^-1 (zero on the last row only; w_n the generator of the trace
+ * domain), next row = (r + 1) mod n.  Arguments and their checks as mh_check_constraints. */
+int mh_constraint_fold(mh_ctx* ctx, const mh_air* air, const mh_trace* main_trace, const mh_trace* aux /* or NULL */,
+                       const mh_trace* preprocessed /* or NULL */, const uint64_t* public_values, size_t n_public,
+                       const uint64_t* randomness /* EF pairs */, size_t n_randomness, const uint64_t* aux_values /* EF pairs */,
+                       size_t n_aux_values, const uint64_t alpha[2], uint64_t* out);
 /* The statements: the arguments of the provers without hash_fn.  Aux columns are built on the device by the attached lookup programs with
  * debug challenges: a Poseidon2 duplex challenger started from the statement's challenger state observes the pre-observe schedule
  * (mh_miden_pre_observe; mh_precompile_pre_observe with 0^4 for the preprocessed commitment), the number of AIRs and their log heights

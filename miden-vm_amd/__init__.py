@@ -37,7 +37,7 @@ EXPORTS = [
     "mh_local_fabric_create", "mh_local_fabric_destroy", "mh_local_fabric_abort", "mh_comm_create_local",
     "mh_miden_load", "mh_miden_free", "mh_prove_miden", "mh_prove_miden_traces", "mh_verify_miden", "mh_miden_pcs_params",
     "mh_miden_challenger_state", "mh_miden_hash_kernel_digests", "mh_miden_pre_observe", "mh_miden_eval_external", "mh_miden_air_blob",
-    "mh_check_constraints", "mh_check_miden", "mh_check_miden_traces", "mh_check_precompile", "mh_check_precompile_traces",
+    "mh_check_constraints", "mh_constraint_fold", "mh_check_miden", "mh_check_miden_traces", "mh_check_precompile", "mh_check_precompile_traces",
     "mh_check_balance", "mh_check_balance_miden", "mh_check_balance_miden_traces", "mh_check_balance_precompile", "mh_check_balance_precompile_traces",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
@@ -650,6 +650,22 @@ def check_constraints(ctx, dev_air, main, aux=None, preprocessed=None, publics=(
 
     entries = _run_check(ctx, call)
     return entries, [int(x) for x in rows[1:1 + int(rows[0])]]
+
+
+def constraint_fold(ctx, dev_air, main, aux=None, preprocessed=None, publics=(), randomness=(), aux_values=(), alpha=(1, 0)):
+    """mh_constraint_fold (a test and diagnostic entry): the fold F(r) = sum_k alpha^(K-1-k) C_k(r) of `dev_air`'s constraints, computed
+    by its own constraint program on the rows of `main` with the screen's selector values (is_first = [r == 0], is_last = [r == n-1],
+    is_transition = w_n^r - w_n^-1).  Arguments as check_constraints; alpha: an EF pair.  -> ndarray[n, 2] of canonical felts."""
+    main, aux, preprocessed = _as_trace(ctx, main), _as_trace(ctx, aux), _as_trace(ctx, preprocessed)
+    pub = _arr([int(x) for x in publics] or [0])
+    rnd = _arr([int(x) for r in randomness for x in r] or [0])
+    av = _arr([int(x) for r in aux_values for x in r] or [0])
+    al = _arr([int(alpha[0]), int(alpha[1])])
+    out = np.zeros((1 << main.log_n, 2), dtype=np.uint64)
+    ctx.check(ctx.lib.mh_constraint_fold(ctx.h, dev_air.h, main.h, aux.h if aux is not None else None,
+                                         preprocessed.h if preprocessed is not None else None, _ptr(pub), C.c_size_t(len(publics)),
+                                         _ptr(rnd), C.c_size_t(len(randomness)), _ptr(av), C.c_size_t(len(aux_values)), _ptr(al), _ptr(out)))
+    return out
 
 
 class DeviceLookup:

@@ -224,9 +224,9 @@ static e2 random_ef() {
   return e2{c0, felt()};
 }
 
-void check_air(mh_ctx* c, const mh_air* air, const mh_trace* main, const mh_trace* aux, const mh_trace* prep, const std::vector<u64>& publics,
-               const std::vector<e2>& randomness, const std::vector<e2>& aux_values, bool exact, int instance,
-               std::vector<mh_check_entry>& out, std::vector<u64>* failing_rows) {
+// the argument checks shared by check_air and mh_constraint_fold -> the preprocessed matrix the AIR reads (null: none)
+static const mh_trace* check_air_args(const mh_air* air, const mh_trace* main, const mh_trace* aux, const mh_trace* prep, size_t n_public,
+                                      size_t n_randomness, size_t n_aux_values) {
   MH_REQUIRE(air && main, "null AIR or trace");
   MH_REQUIRE(main->width == air->main_width, "trace width does not match the AIR");
   MH_REQUIRE(main->log_n >= 1, "trace needs at least 2 rows");
@@ -244,9 +244,18 @@ void check_air(mh_ctx* c, const mh_air* air, const mh_trace* main, const mh_trac
   } else {
     prep = nullptr;
   }
-  MH_REQUIRE(publics.size() == air->num_public, "AIR expects a different number of public values");
-  MH_REQUIRE(randomness.size() >= air->num_randomness, "not enough randomness for the AIR");
-  MH_REQUIRE(aux_values.size() >= air->num_aux_values, "not enough aux values for the AIR");
+  MH_REQUIRE(n_public == air->num_public, "AIR expects a different number of public values");
+  MH_REQUIRE(n_randomness >= air->num_randomness, "not enough randomness for the AIR");
+  MH_REQUIRE(n_aux_values >= air->num_aux_values, "not enough aux values for the AIR");
+  return prep;
+}
+
+void check_air(mh_ctx* c, const mh_air* air, const mh_trace* main, const mh_trace* aux, const mh_trace* prep, const std::vector<u64>& publics,
+               const std::vector<e2>& randomness, const std::vector<e2>& aux_values, bool exact, int instance,
+               std::vector<mh_check_entry>& out, std::vector<u64>* failing_rows) {
+  prep = check_air_args(air, main, aux, prep, publics.size(), randomness.size(), aux_values.size());
+  const int log_n = main->log_n;
+  const size_t n = (size_t)1 << log_n;
   if (failing_rows) failing_rows->clear();
   const size_t K = air->n_constraints;
   if (!K) return;
@@ -485,6 +494,60 @@ extern "C" int mh_check_constraints(mh_ctx* c, const mh_air* air, const mh_trace
       std::copy(rows.begin(), rows.end(), failing_rows + 1);
     }
     return report(c, entries, nullptr, out, cap, n_entries);
+  } catch (const MhError& e) {
+    c->err = e.what();
+    return e.code;
+  } catch (const std::exception& e) {
+    c->err = e.what();
+    return MH_ERR_INTERNAL;
+  }
+}
+
+// accumulator planes [2][n], any representative -> canonical EF pairs [n][2]
+__global__ void k_fold_pairs(const u64* __restrict__ acc, size_t n, u64* __restrict__ out) {
+  const size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  out[2 * r] = gl_canon(acc[r]);
+  out[2 * r + 1] = gl_canon(acc[n + r]);
+}
+
+// Test and diagnostic entry (as mh_pcs_download_deep is): the screen's fold itself, with the caller's alpha instead of a fresh random one.
+// out [n][2] receives F(r) = sum_k alpha^(K-1-k) s_k(r) C_k(r) as canonical EF pairs, computed by the AIR's own constraint program on the
+// trace domain (quotient.hip constraint_fold_trace_domain: compiled chunks or interpreter, whichever mh_air_load chose) with the screen's
+// selector values: x = w_n^r, Z_H = 1/Z_H = 1, is_first = [r == 0], is_last = [r == n-1], is_transition = w_n^r - w_n^-1 (zero on the
+// last row only, NOT [r != n-1]), next row = (r + 1) mod n.  K = 0: all zero.
+extern "C" int mh_constraint_fold(mh_ctx* c, const mh_air* air, const mh_trace* main_trace, const mh_trace* aux, const mh_trace* preprocessed,
+                                  const uint64_t* public_values, size_t n_public, const uint64_t* randomness, size_t n_randomness,
+                                  const uint64_t* aux_values, size_t n_aux_values, const uint64_t alpha[2], uint64_t* out) {
+  if (!c) return MH_ERR_INVALID;
+  PoolScope _ps(c);
+  try {
+    MH_REQUIRE(air && main_trace && alpha && out, "null argument");
+    MH_REQUIRE(air->ctx == c && main_trace->ctx == c && (!aux || aux->ctx == c), "AIR / trace of another context");
+    MH_REQUIRE_NO_SALT(c, "mh_constraint_fold");
+    MH_REQUIRE((public_values || !n_public) && (randomness || !n_randomness) && (aux_values || !n_aux_values), "null value array");
+    HIP_CHECK(hipSetDevice(c->device));
+    std::vector<u64> pub(public_values, public_values + n_public);
+    std::vector<e2> rnd, av;
+    for (size_t i = 0; i < n_randomness; i++) rnd.push_back(e2{gl_canon(randomness[2 * i]), gl_canon(randomness[2 * i + 1])});
+    for (size_t i = 0; i < n_aux_values; i++) av.push_back(e2{gl_canon(aux_values[2 * i]), gl_canon(aux_values[2 * i + 1])});
+    const mh_trace* prep = check_air_args(air, main_trace, aux, preprocessed, n_public, n_randomness, n_aux_values);
+    const size_t n = (size_t)1 << main_trace->log_n;
+    if (!air->n_constraints) {
+      std::fill(out, out + 2 * n, (uint64_t)0);
+      return MH_OK;
+    }
+    trace_wait_ready(c, main_trace);
+    trace_wait_ready(c, aux);
+    trace_wait_ready(c, prep);
+    DevBuf sel(2 * n * 8), acc(2 * n * 8), pairs(2 * n * 8);
+    MH_LAUNCH(k_check_selectors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, sel.u(), sel.u() + n, n);
+    constraint_fold_trace_domain(c, air, main_trace, aux, prep, sel.u(), sel.u() + n, pub, rnd, av,
+                                 e2{gl_canon(alpha[0]), gl_canon(alpha[1])}, acc.u());
+    MH_LAUNCH(k_fold_pairs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, acc.u(), n, pairs.u());
+    c->d2h(out, pairs.p, 2 * n * 8);
+    c->sync();
+    return MH_OK;
   } catch (const MhError& e) {
     c->err = e.what();
     return e.code;

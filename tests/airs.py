@@ -209,6 +209,37 @@ def logup_trace(log_n, seed=3, valid=True):
     return t
 
 
+# challenges with corner components for logup_corner_trace (tests/test_jit_corner_operands.py checks on the CPU that no denominator
+# vanishes under them)
+LOGUP_CORNER_CHALLENGES = [[(P - 1, 0xFFFFFFFEFFFFFFFF), ((1 << 32) - 1, 1 << 32)],
+                           [(0xFFFFFFFEFFFFFFFF, 1), (P - 1, P - 1)],
+                           [(1 << 32, (1 << 32) - 1), (0xFFFFFFFEFFFFFFFF, 0xFFFFFFFEFFFFFFFF)]]
+
+
+def logup_corner_trace(log_n, valid=True):
+    """logup_trace's structure (V looked up in T with multiplicities M, B a permutation of A, F[r] = E[r+1]) with every value column
+    filled from the corner operand table of tests/jit_corner_operands.py: the compiled lookup program's products and sums see the
+    operands that reach the rare carries of the asm product."""
+    import jit_corner_operands as J
+    n = 1 << log_n
+    rng = np.random.default_rng(log_n)
+    col = lambda shift, which: np.array(J.column_values(n, shift, which), dtype=np.uint64)
+    t = np.zeros((n, 8), dtype=np.uint64)
+    table = col(0, 0)
+    picks = rng.integers(0, n, n)
+    t[:, 0] = table[picks]
+    t[:, 1] = table
+    t[:, 2] = np.bincount(picks, minlength=n).astype(np.uint64)
+    t[:, 3] = col(0, 1)
+    t[:, 4] = rng.permutation(t[:, 3])
+    t[:, 5] = col(37, 0)
+    t[:, 6] = col(59, 1)
+    t[:, 7] = np.roll(t[:, 6], -1)
+    if not valid:
+        t[n // 2, 0] = (int(t[n // 2, 0]) + 1) % P
+    return t
+
+
 # ------------------------------------------------------------------------------------------------
 def prep_air(log_n, seed=13, num_public=0):
     """An AIR with PREPROCESSED columns (fixed circuit data committed at setup, crates/lifted-stark/src/preprocessed.rs):

@@ -5,7 +5,7 @@ import os, re, shutil, subprocess
 import pytest
 from __graft_entry__ import load_package, ROOT
 
-CHECK_FUNCS = ["mh_check_constraints", "mh_check_miden", "mh_check_miden_traces", "mh_check_precompile", "mh_check_precompile_traces"]
+CHECK_FUNCS = ["mh_check_constraints", "mh_constraint_fold", "mh_check_miden", "mh_check_miden_traces", "mh_check_precompile", "mh_check_precompile_traces"]
 
 
 def header():

@@ -9,6 +9,7 @@ import pytest
 import oracle_binding as ob
 import airs as A
 import ref_traces as RT
+from dag_eval import evaluate
 from __graft_entry__ import load_package
 from miden_vm_amd import dag, core_air as CO, precompile_airs as PA
 from miden_vm_amd.testing import precompile_trace as PT
@@ -39,73 +40,7 @@ def device_air(ctx, air, jit):
             os.environ["MH_JIT"] = old
 
 
-# ---- an independent evaluation: the blob's DAG over Python integers, EF = F_p[x] / (x^2 - 7) ----
-W = 7
-
-
-def ef(v):
-    return v if isinstance(v, tuple) else (v % P, 0)
-
-
-def e_add(a, b):
-    return ((a[0] + b[0]) % P, (a[1] + b[1]) % P)
-
-
-def e_sub(a, b):
-    return ((a[0] - b[0]) % P, (a[1] - b[1]) % P)
-
-
-def e_mul(a, b):
-    return ((a[0] * b[0] + W * a[1] * b[1]) % P, (a[0] * b[1] + a[1] * b[0]) % P)
-
-
-def parse(blob):
-    w = [int(x) for x in blob]
-    n_periodic, n_nodes, n_cons = w[6], w[8], w[9]
-    k, periodic = 12, []
-    for _ in range(n_periodic):
-        ln = w[k]
-        periodic.append(w[k + 1:k + 1 + ln])
-        k += 1 + ln
-    nodes = []
-    for _ in range(n_nodes):
-        x, c = w[k], w[k + 1]
-        nodes.append((x & 0xFF, (x >> 8) & ((1 << 28) - 1), x >> 36, c))
-        k += 2
-    return periodic, nodes, w[k:k + n_cons]
-
-
-def evaluate(air, main, aux, prep, publics, rnd, aux_values):
-    """-> {constraint: (rows, first_row, value at first_row)} of every constraint that does not vanish somewhere."""
-    periodic, nodes, cons = parse(air.blob)
-    n = main.shape[0]
-    out = {}
-    for r in range(n):
-        rows = (r, (r + 1) % n)
-        val = []
-        for op, a, b, c in nodes:
-            if op == dag.OP_CONST: v = ef(c)
-            elif op == dag.OP_MAIN: v = ef(int(main[rows[b], a]))
-            elif op == dag.OP_AUX: v = (int(aux[rows[b], 2 * a]) % P, int(aux[rows[b], 2 * a + 1]) % P)
-            elif op == dag.OP_PREPROCESSED: v = ef(int(prep[rows[b], a]))
-            elif op == dag.OP_PUBLIC: v = ef(publics[a])
-            elif op == dag.OP_PERIODIC: v = ef(periodic[a][r % len(periodic[a])])
-            elif op == dag.OP_IS_FIRST: v = ef(int(r == 0))
-            elif op == dag.OP_IS_LAST: v = ef(int(r == n - 1))
-            elif op == dag.OP_IS_TRANSITION: v = ef(int(r != n - 1))
-            elif op == dag.OP_RANDOMNESS: v = tuple(x % P for x in rnd[a])
-            elif op == dag.OP_AUX_VALUE: v = tuple(x % P for x in aux_values[a])
-            elif op == dag.OP_ADD: v = e_add(val[a], val[b])
-            elif op == dag.OP_SUB: v = e_sub(val[a], val[b])
-            elif op == dag.OP_MUL: v = e_mul(val[a], val[b])
-            elif op == dag.OP_NEG: v = e_sub((0, 0), val[a])
-            else: raise AssertionError(op)
-            val.append(v)
-        for k, nid in enumerate(cons):
-            if val[nid] != (0, 0):
-                cnt, first, fv = out.get(k, (0, r, val[nid]))
-                out[k] = (cnt + 1, first, fv)
-    return out
+# the independent evaluation (the blob's DAG over Python integers) lives in tests/dag_eval.py, shared with the fold tests
 
 
 def as_dict(entries):

@@ -38,6 +38,28 @@ def test_device_aux_trace_equals_oracle(ctx, log_n, valid):
     assert (fin == (0, 0)) == valid
 
 
+@pytest.mark.parametrize("log_n", [4, 8])
+def test_device_aux_trace_on_corner_operands_equals_oracle(ctx, log_n):
+    """The main columns hold the corner operand table (tests/jit_corner_operands.py: values that reach the rare carries of the compiled
+    programs' asm product), the challenges have corner components; tests/test_jit_corner_operands.py checks on the CPU that no
+    denominator vanishes.  Aux trace and accumulator final equal the oracle's, cell for cell."""
+    pkg = load_package()
+    _, lookup = A.logup_air()
+    dl = pkg.DeviceLookup(ctx, lookup)
+    for valid in (True, False):
+        main = A.logup_corner_trace(log_n, valid=valid)
+        tm = ctx.upload_trace(main)
+        for rnd in A.LOGUP_CORNER_CHALLENGES:
+            aux_dev, fin = dl.build_aux(tm, rnd)
+            aux, exp_fin = ob.lookup_build_aux(lookup, main, rnd)
+            got = aux_dev.download()
+            assert got.shape == aux.shape
+            bad = np.argwhere(got != aux)
+            assert bad.size == 0, f"valid={valid} rnd={rnd}: first differing aux cell (row, col) = {bad[0]}"
+            assert fin == (int(exp_fin[0]), int(exp_fin[1]))
+            assert (fin == (0, 0)) == valid
+
+
 def test_proof_with_device_built_aux_equals_oracle(ctx):
     pkg = load_package()
     for log_n in (5, 9):
