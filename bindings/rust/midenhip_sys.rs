@@ -96,6 +96,36 @@ pub struct mh_lmcs_opening {
     pub commitments: *const u64,
     pub n_commit_felts: usize,
 }
+/// The caller's buffers for one opening of mh_lmcs_witness_batch, sized by mh_lmcs_witness_size; nodes may be null.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct mh_lmcs_witness_out {
+    pub leaf_digests: *mut u64,
+    pub paths: *mut u64,
+    pub nodes: *mut u64,
+}
+/// mh_verify_batch_witness's result: per accepted item one witness per LMCS opening of the proof.
+#[repr(C)]
+pub struct mh_witness_set {
+    _private: [u8; 0],
+}
+/// One tree of an mh_witness_set; every pointer points into memory the set owns.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct mh_witness_tree {
+    pub kind: c_int,
+    pub which: c_int,
+    pub depth: c_int,
+    pub n_leaves: usize,
+    pub n_nodes: usize,
+    pub row_len: usize,
+    pub root: [u64; 4],
+    pub indices: *const u64,
+    pub rows: *const u64,
+    pub leaf_digests: *const u64,
+    pub paths: *const u64,
+    pub nodes: *const u64,
+}
 /// What differs per proof of an mh_verify_batch call.
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -335,6 +365,18 @@ unsafe extern "C" {
     pub fn mh_lmcs_verify_batch(ctx: *mut mh_ctx, lmcs: c_int, salt_elems: c_int, n: usize, items: *const mh_lmcs_opening, ok: *mut c_int) -> c_int;
     /// mh_verify_hiding for many proofs of one statement shape: host replay per item, every opening hashed on the device
     pub fn mh_verify_batch(ctx: *mut mh_ctx, lmcs: c_int, salt_elems: c_int, params: *const mh_pcs_params, n_airs: c_int, air_blobs: *const *const u64, air_blob_words: *const usize, challenger_state: *const u64, external: mh_external_assertions, n_items: usize, items: *const mh_verify_item, results: *mut mh_verify_result) -> c_int;
+    /// an opening read back as a Merkle witness: shape only (any index order, duplicates allowed)
+    pub fn mh_lmcs_witness_size(o: *const mh_lmcs_opening, n_leaves: *mut usize, n_nodes: *mut usize, err: *mut c_char, err_cap: usize) -> c_int;
+    /// host only: leaf_digests[k][4], paths[k][depth][4], nodes[n_nodes][4] (or null); MH_OK exactly when mh_lmcs_verify accepts
+    pub fn mh_lmcs_witness(lmcs: c_int, salt_elems: c_int, o: *const mh_lmcs_opening, leaf_digests: *mut u64, paths: *mut u64, nodes: *mut u64, err: *mut c_char, err_cap: usize) -> c_int;
+    /// the same for n openings on the device; for ok[i] = 0 the item's buffers are untouched
+    pub fn mh_lmcs_witness_batch(ctx: *mut mh_ctx, lmcs: c_int, salt_elems: c_int, n: usize, items: *const mh_lmcs_opening, outs: *const mh_lmcs_witness_out, ok: *mut c_int) -> c_int;
+    /// mh_verify_batch that hands back the witnesses of every accepted item's openings, in proof order
+    pub fn mh_verify_batch_witness(ctx: *mut mh_ctx, lmcs: c_int, salt_elems: c_int, params: *const mh_pcs_params, n_airs: c_int, air_blobs: *const *const u64, air_blob_words: *const usize, challenger_state: *const u64, external: mh_external_assertions, n_items: usize, items: *const mh_verify_item, results: *mut mh_verify_result, out: *mut *mut mh_witness_set) -> c_int;
+    pub fn mh_witness_set_trees(set: *const mh_witness_set, item: usize) -> usize;
+    pub fn mh_witness_set_tree(set: *const mh_witness_set, item: usize, t: usize, view: *mut mh_witness_tree) -> c_int;
+    pub fn mh_witness_set_free(set: *mut mh_witness_set);
+    pub fn mh_verify_miden_batch_witness(ctx: *mut mh_ctx, hash_fn: c_int, n: usize, items: *const mh_miden_verify_item, results: *mut mh_verify_result, out: *mut *mut mh_witness_set) -> c_int;
     pub fn mh_miden_pcs_params(out: *mut mh_pcs_params);
     pub fn mh_miden_challenger_state(state: *mut u64);
     pub fn mh_miden_hash_kernel_digests(kernel_felts: *const u64, n_felts: usize, out: *mut u64) -> c_int;

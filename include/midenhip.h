@@ -591,6 +591,35 @@ int mh_lmcs_verify(int lmcs, int salt_elems, const mh_lmcs_opening* o, char* err
  * host call for those); the reason is mh_last_error's.  n = 0 is MH_OK. */
 int mh_lmcs_verify_batch(mh_ctx* ctx, int lmcs, int salt_elems, size_t n, const mh_lmcs_opening* items, int* ok);
 
+/* ---- an opening read back as a Merkle witness (the reference's BatchProofView / MerkleWitness, lmcs/proof.rs:42-80) -----------------
+ * What the verifier of an opening derives on its way to the root, kept: for depth = log_height and the k DISTINCT opened indices
+ * i_0 < ... < i_{k-1}, three arrays of 4-word digests, packed as mh_tree_root packs them:
+ *   leaf_digests[k][4]      the hash of opened leaf q (its aligned rows, then its salt), ascending index order;
+ *   paths[k][depth][4]      paths[q][l] = the digest of node (i_q >> l) ^ 1 on level l above the leaves, bottom to top
+ *                           (MerkleWitness::path(i_q)): a streamed sibling where the proof carries one, otherwise a leaf digest or a
+ *                           derived node of the same opening;
+ *   nodes[n_nodes][4]       every derived parent, level by level from the leaves' parents up, ascending position within a level;
+ *                           node j of level l is the j-th distinct value of i >> (l + 1); the last entry is the root.
+ * depth 0: k = 1, no path element, no node, leaf_digests[0] is the root.
+ * mh_lmcs_witness_size: shape only (k and n_nodes) from log_height and the indices, which may come in any order and with duplicates;
+ * it refuses what mh_lmcs_verify's index checks refuse, with the same reason.
+ * mh_lmcs_witness: HOST ONLY.  MH_OK exactly when mh_lmcs_verify accepts the same arguments; otherwise its code and its reason, and
+ * nothing is written to the buffers.  `nodes` may be NULL; a NULL leaf_digests or paths (depth > 0) is refused. */
+int mh_lmcs_witness_size(const mh_lmcs_opening* o, size_t* n_leaves, size_t* n_nodes, char* err, size_t err_cap);
+int mh_lmcs_witness(int lmcs, int salt_elems, const mh_lmcs_opening* o, uint64_t* leaf_digests, uint64_t* paths, uint64_t* nodes /* or NULL */,
+                    char* err, size_t err_cap);
+/* The same for n openings on the DEVICE, in mh_lmcs_verify_batch's passes: the leaf kernel's digests are kept, and a witness form of
+ * the path kernel stores every parent and copies every path element while it walks the levels.  One read-back per pass, in the final
+ * layout.  outs[i] = the caller's buffers for items[i], sized by mh_lmcs_witness_size (nodes may be NULL).  ok[i] = 1 iff
+ * mh_lmcs_witness accepts items[i] and then outs[i] holds what it writes; for ok[i] = 0 the item's buffers are untouched.  Call-level
+ * refusals, kernel bounds and MH_VERIFY_BATCH_BYTES as mh_lmcs_verify_batch. */
+typedef struct mh_lmcs_witness_out {
+  uint64_t* leaf_digests;
+  uint64_t* paths;
+  uint64_t* nodes; /* or NULL */
+} mh_lmcs_witness_out;
+int mh_lmcs_witness_batch(mh_ctx* ctx, int lmcs, int salt_elems, size_t n, const mh_lmcs_opening* items, const mh_lmcs_witness_out* outs, int* ok);
+
 /* mh_verify_hiding for MANY proofs of one statement shape: the AIR list, the parameters, the challenger state and the external
  * assertions are the batch's, an item carries what differs per proof.  For a node that sits beside the provers and accepts many
  * proofs before it aggregates them; a verifier box without a GPU keeps mh_verify*.  Each item is replayed on the host (transcript,
@@ -631,6 +660,31 @@ typedef struct mh_verify_result {
 int mh_verify_batch(mh_ctx* ctx, int lmcs, int salt_elems, const mh_pcs_params* params, int n_airs, const uint64_t* const* air_blobs,
                     const size_t* air_blob_words, const uint64_t challenger_state[12], mh_external_assertions external, size_t n_items,
                     const mh_verify_item* items, mh_verify_result* results);
+/* mh_verify_batch that also hands back what it derived: verdicts, digests and reasons are exactly mh_verify_batch's, and *out
+ * receives a set (free it with mh_witness_set_free) that holds, for every ACCEPTED item, one witness (mh_lmcs_witness*) per LMCS
+ * opening of the proof, in proof order: the committed trees [preprocessed?, main, aux, quotient], then FRI round 0, 1, ...  A rejected
+ * item carries none.  This is what a recursive verifier's advice needs per tree: a leaf hash and a Merkle path per query, the inner
+ * nodes, and the opened rows behind every leaf hash.  Every pointer of a view points into memory the set owns, `rows` included (a
+ * copy of the proof's field stream: the set outlives the caller's buffers).  On a call-level failure *out is NULL. */
+typedef struct mh_witness_set mh_witness_set;
+typedef struct mh_witness_tree {
+  int kind;  /* 0: a committed tree, 1: an FRI round tree */
+  int which; /* which tree of that kind */
+  int depth;
+  size_t n_leaves, n_nodes, row_len; /* row_len: felts per opened leaf (every matrix's aligned row, then the salt) */
+  uint64_t root[4];
+  const uint64_t* indices;      /* [n_leaves], ascending */
+  const uint64_t* rows;         /* [n_leaves][row_len] */
+  const uint64_t* leaf_digests; /* [n_leaves][4] */
+  const uint64_t* paths;        /* [n_leaves][depth][4] */
+  const uint64_t* nodes;        /* [n_nodes][4] */
+} mh_witness_tree;
+int mh_verify_batch_witness(mh_ctx* ctx, int lmcs, int salt_elems, const mh_pcs_params* params, int n_airs, const uint64_t* const* air_blobs,
+                            const size_t* air_blob_words, const uint64_t challenger_state[12], mh_external_assertions external, size_t n_items,
+                            const mh_verify_item* items, mh_verify_result* results, mh_witness_set** out);
+size_t mh_witness_set_trees(const mh_witness_set* set, size_t item); /* 0 for a rejected item or an item out of range */
+int mh_witness_set_tree(const mh_witness_set* set, size_t item, size_t t, mh_witness_tree* view);
+void mh_witness_set_free(mh_witness_set* set);
 
 /* ---- the precompile prover's session: SessionTraces::prove_stark's own shape (precompiles-prover/src/session/prove.rs:295-330, 385-416)
  * Twelve main traces + the transcript root in, proof out -- the statement layer `ChipletMultiAir` adds to the proof system, in the
@@ -715,6 +769,9 @@ typedef struct mh_miden_verify_item {
   size_t n_bytes;
 } mh_miden_verify_item;
 int mh_verify_miden_batch(mh_ctx* ctx, int hash_fn, size_t n, const mh_miden_verify_item* items, mh_verify_result* results);
+/* the same through mh_verify_batch_witness: set item i = proof i (none for an item rejected before or in the batch) */
+int mh_verify_miden_batch_witness(mh_ctx* ctx, int hash_fn, size_t n, const mh_miden_verify_item* items, mh_verify_result* results,
+                                  mh_witness_set** out);
 /* the pieces, for a caller that drives mh_prove / mh_session_* / mh_verify_ex itself */
 void mh_miden_pcs_params(mh_pcs_params* out);
 void mh_miden_challenger_state(uint64_t state[12]);

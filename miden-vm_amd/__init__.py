@@ -44,6 +44,8 @@ EXPORTS = [
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
     "mh_pcs_fri_fold", "mh_pcs_fri_final", "mh_pcs_query", "mh_pcs_open", "mh_pcs_verify", "mh_session_trees",
     "mh_lmcs_verify", "mh_lmcs_verify_batch", "mh_verify_batch", "mh_verify_miden_batch",
+    "mh_lmcs_witness_size", "mh_lmcs_witness", "mh_lmcs_witness_batch", "mh_verify_batch_witness", "mh_witness_set_trees",
+    "mh_witness_set_tree", "mh_witness_set_free", "mh_verify_miden_batch_witness",
 ]
 
 MH_MAX_SALT_ELEMS = 8  # mh_ctx_set_salt: the largest salt width of the hiding LMCS
@@ -501,6 +503,11 @@ class LmcsTree:
         """mh_lmcs_verify (host only) of an opening of this tree: (True, "") or (False, reason)."""
         lmcs = {v: k for k, v in Ctx.LMCS.items()}[self.ctx.lib.mh_ctx_get_lmcs(self.ctx.h)]
         return lmcs_verify(self.opening(indices, fields, commitments, alignment), lmcs, self.salt_elems)
+
+    def witness(self, indices, fields, commitments, alignment=8):
+        """mh_lmcs_witness (host only) of an opening of this tree: the LmcsWitness; raises MidenHipError with the reason if refused."""
+        lmcs = {v: k for k, v in Ctx.LMCS.items()}[self.ctx.lib.mh_ctx_get_lmcs(self.ctx.h)]
+        return lmcs_witness(self.opening(indices, fields, commitments, alignment), lmcs, self.salt_elems)
 
     def download_lde(self, mat):
         rows = 1 << (self.log_heights[mat] + self.log_blowup)
@@ -1168,6 +1175,129 @@ def lmcs_verify_batch(ctx, openings, lmcs="poseidon2", salt_elems=0):
     return [int(ok[i]) for i in range(len(items))]
 
 
+# ---- openings read back as Merkle witnesses (mh_lmcs_witness*, mh_verify_batch_witness) ---------------------------------------------
+class LmcsWitness:
+    """What the verifier of one opening derives: indices (sorted, unique), leaf_digests[k][4], paths[k][depth][4], nodes[n_nodes][4]
+    (None if not asked for).  path(i) = the authentication path of opened leaf i, bottom to top; root() = the derived root."""
+
+    def __init__(self, indices, leaf_digests, paths, nodes):
+        self.indices, self.leaf_digests, self.paths, self.nodes = indices, leaf_digests, paths, nodes
+
+    @property
+    def depth(self):
+        return self.paths.shape[1]
+
+    def path(self, i):
+        q = int(np.searchsorted(self.indices, np.uint64(i)))
+        if q >= self.indices.size or int(self.indices[q]) != int(i):
+            raise KeyError(f"leaf {i} is not opened")
+        return self.paths[q]
+
+    def root(self):
+        if self.depth == 0:
+            return self.leaf_digests[0]
+        if self.nodes is None:
+            raise MidenHipError("LmcsWitness.root: the witness was made without its nodes")
+        return self.nodes[-1]
+
+
+class LmcsWitnessOut(C.Structure):
+    _fields_ = [("leaf_digests", u64p), ("paths", u64p), ("nodes", u64p)]
+
+
+def lmcs_witness_size(opening):
+    """mh_lmcs_witness_size: (n_leaves, n_nodes) of the witness of an opening (only its height and indices are read)."""
+    lib = load_library()
+    items, arr = _openings([opening])
+    k, m, err = C.c_size_t(0), C.c_size_t(0), C.create_string_buffer(512)
+    lib.mh_lmcs_witness_size.argtypes = [C.POINTER(LmcsOpening), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
+    if lib.mh_lmcs_witness_size(arr, C.byref(k), C.byref(m), err, 512) != 0:
+        raise MidenHipError(err.value.decode())
+    return k.value, m.value
+
+
+def _witness_buffers(o, nodes=True):
+    k, m = lmcs_witness_size(o)
+    idx = np.unique(np.array([int(o.indices[i]) for i in range(o.n_indices)], dtype=np.uint64))
+    return LmcsWitness(idx, np.zeros((k, 4), dtype=np.uint64), np.zeros((k, o.log_height, 4), dtype=np.uint64),
+                       np.zeros((m, 4), dtype=np.uint64) if nodes else None)
+
+
+def lmcs_witness(opening, lmcs="poseidon2", salt_elems=0, nodes=True):
+    """mh_lmcs_witness (host only): the LmcsWitness of an opening mh_lmcs_verify accepts; MidenHipError with its reason otherwise."""
+    lib = load_library()
+    items, arr = _openings([opening])
+    w = _witness_buffers(items[0], nodes)
+    err = C.create_string_buffer(512)
+    lib.mh_lmcs_witness.argtypes = [C.c_int, C.c_int, C.POINTER(LmcsOpening), C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    rc = lib.mh_lmcs_witness(Ctx.LMCS[lmcs], int(salt_elems), arr, w.leaf_digests.ctypes.data, w.paths.ctypes.data,
+                             w.nodes.ctypes.data if nodes else None, err, 512)
+    if rc != 0:
+        raise MidenHipError(err.value.decode())
+    return w
+
+
+def lmcs_witness_batch(ctx, openings, lmcs="poseidon2", salt_elems=0, nodes=True):
+    """mh_lmcs_witness_batch: the openings hashed on the device and read back as witnesses; per opening its LmcsWitness, or None
+    where mh_lmcs_witness refuses it."""
+    items, arr = _openings(openings)
+    ws = []
+    for o in items:
+        try:
+            ws.append(_witness_buffers(o, nodes))
+        except MidenHipError:  # an index the shape check refuses: the call itself gives the verdict 0, its buffers are never written
+            ws.append(LmcsWitness(np.zeros(0, dtype=np.uint64), np.zeros((1, 4), dtype=np.uint64), np.zeros((1, 1, 4), dtype=np.uint64), None))
+    outs = (LmcsWitnessOut * max(1, len(items)))()
+    for k, w in enumerate(ws):
+        outs[k].leaf_digests, outs[k].paths = _ptr(w.leaf_digests), C.cast(w.paths.ctypes.data, u64p)
+        outs[k].nodes = _ptr(w.nodes) if w.nodes is not None and w.nodes.size else None
+    ok = (C.c_int * max(1, len(items)))()
+    ctx.lib.mh_lmcs_witness_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(LmcsOpening), C.POINTER(LmcsWitnessOut),
+                                              C.POINTER(C.c_int)]
+    ctx.check(ctx.lib.mh_lmcs_witness_batch(ctx.h, Ctx.LMCS[lmcs], int(salt_elems), len(items), arr, outs, ok))
+    return [w if ok[k] else None for k, w in enumerate(ws)]
+
+
+class WitnessTreeView(C.Structure):
+    _fields_ = [("kind", C.c_int), ("which", C.c_int), ("depth", C.c_int), ("n_leaves", C.c_size_t), ("n_nodes", C.c_size_t),
+                ("row_len", C.c_size_t), ("root", C.c_uint64 * 4), ("indices", u64p), ("rows", u64p), ("leaf_digests", u64p), ("paths", u64p),
+                ("nodes", u64p)]
+
+
+class WitnessTree(LmcsWitness):
+    """One tree of a verified proof (mh_witness_tree), copied out of the set: an LmcsWitness plus kind (0 committed, 1 FRI round),
+    which, tree_root (the proof's commitment) and rows[k][row_len] (the opened rows behind the leaf digests)."""
+
+
+def _witness_sets(lib, handle, n):
+    """the trees of every item of an mh_witness_set as Python objects; frees the set"""
+    def take(p, shape):
+        size = int(np.prod(shape))
+        return np.ctypeslib.as_array(p, shape=(size,)).reshape(shape).copy() if size else np.zeros(shape, dtype=np.uint64)
+    lib.mh_witness_set_trees.restype = C.c_size_t
+    lib.mh_witness_set_trees.argtypes = [C.c_void_p, C.c_size_t]
+    lib.mh_witness_set_tree.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(WitnessTreeView)]
+    lib.mh_witness_set_free.argtypes = [C.c_void_p]
+    lib.mh_witness_set_free.restype = None
+    try:
+        out = []
+        for i in range(n):
+            trees = []
+            for t in range(lib.mh_witness_set_trees(handle, i)):
+                v = WitnessTreeView()
+                if lib.mh_witness_set_tree(handle, i, t, C.byref(v)) != 0:
+                    raise MidenHipError("mh_witness_set_tree failed")
+                w = WitnessTree(take(v.indices, (v.n_leaves,)), take(v.leaf_digests, (v.n_leaves, 4)), take(v.paths, (v.n_leaves, v.depth, 4)),
+                                take(v.nodes, (v.n_nodes, 4)))
+                w.kind, w.which, w.tree_root = int(v.kind), int(v.which), np.array(list(v.root), dtype=np.uint64)
+                w.rows = take(v.rows, (v.n_leaves, v.row_len))
+                trees.append(w)
+            out.append(trees)
+        return out
+    finally:
+        lib.mh_witness_set_free(handle)
+
+
 class VerifyItem(C.Structure):
     _fields_ = [("log_trace_heights", C.POINTER(C.c_uint8)), ("public_values", u64p), ("n_public_values", C.c_size_t),
                 ("pre_observe", u64p), ("n_pre_observe", C.c_size_t), ("fields", u64p), ("n_fields", C.c_size_t),
@@ -1182,10 +1312,12 @@ def _results(res, n):
     return [(True, np.array(list(res[i].digest), dtype=np.uint64)) if res[i].code == 0 else (False, res[i].reason.decode()) for i in range(n)]
 
 
-def verify_batch(ctx, airs, items, params, challenger_state, external=None, lmcs="poseidon2", salt_elems=0):
+def verify_batch(ctx, airs, items, params, challenger_state, external=None, lmcs="poseidon2", salt_elems=0, witness=False):
     """mh_verify_batch: many proofs of one statement shape -- host replay per item, every LMCS opening of the batch hashed on the
     device.  items = dicts with log_trace_heights, public_values, pre_observe, fields, commitments and optionally
-    preprocessed_root; external as in verify().  Returns per item what verify() returns: (True, digest) or (False, reason)."""
+    preprocessed_root; external as in verify().  Returns per item what verify() returns: (True, digest) or (False, reason).
+    witness=True (mh_verify_batch_witness): returns (that list, per item the list of its WitnessTree -- one per opening of an accepted
+    proof in proof order, [] for a rejected one)."""
     lib = ctx.lib
     n = len(airs)
     blobs = [_arr(a.blob) for a in airs]
@@ -1215,8 +1347,14 @@ def verify_batch(ctx, airs, items, params, challenger_state, external=None, lmcs
     res = (VerifyResult * max(1, len(items)))()
     lib.mh_verify_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(PcsParams), C.c_int, C.POINTER(u64p), C.POINTER(C.c_size_t), u64p,
                                     EXTERNAL_FN, C.c_size_t, C.POINTER(VerifyItem), C.POINTER(VerifyResult)]
-    ctx.check(lib.mh_verify_batch(ctx.h, Ctx.LMCS[lmcs], int(salt_elems), C.byref(p), n, bp, bl, _ptr(st),
-                                  external if external is not None else C.cast(None, EXTERNAL_FN), len(items), arr, res))
+    ext = external if external is not None else C.cast(None, EXTERNAL_FN)
+    if witness:
+        handle = C.c_void_p()
+        lib.mh_verify_batch_witness.argtypes = lib.mh_verify_batch.argtypes + [C.POINTER(C.c_void_p)]
+        ctx.check(lib.mh_verify_batch_witness(ctx.h, Ctx.LMCS[lmcs], int(salt_elems), C.byref(p), n, bp, bl, _ptr(st), ext, len(items), arr, res,
+                                              C.byref(handle)))
+        return _results(res, len(items)), _witness_sets(lib, handle, len(items))
+    ctx.check(lib.mh_verify_batch(ctx.h, Ctx.LMCS[lmcs], int(salt_elems), C.byref(p), n, bp, bl, _ptr(st), ext, len(items), arr, res))
     return _results(res, len(items))
 
 
@@ -1316,8 +1454,9 @@ class MidenVerifyItem(C.Structure):
     _fields_ = [("public_values", u64p), ("aux_inputs", u64p), ("n_aux_inputs", C.c_size_t), ("proof_bytes", C.c_void_p), ("n_bytes", C.c_size_t)]
 
 
-def verify_miden_batch(ctx, items, hash_fn="poseidon2"):
-    """mh_verify_miden_batch: items = (public_values, aux_inputs, proof_bytes) per proof; per item what verify_miden returns."""
+def verify_miden_batch(ctx, items, hash_fn="poseidon2", witness=False):
+    """mh_verify_miden_batch: items = (public_values, aux_inputs, proof_bytes) per proof; per item what verify_miden returns.
+    witness=True (mh_verify_miden_batch_witness): (that list, per item its WitnessTree list) as verify_batch(witness=True)."""
     n = len(items)
     arr = (MidenVerifyItem * max(1, n))()
     keep = []
@@ -1328,6 +1467,12 @@ def verify_miden_batch(ctx, items, hash_fn="poseidon2"):
         arr[k].public_values, arr[k].aux_inputs, arr[k].n_aux_inputs = _ptr(pv), _ptr(aux), len(aux_inputs)
         arr[k].proof_bytes, arr[k].n_bytes = C.cast(buf, C.c_void_p), len(proof_bytes)
     res = (VerifyResult * max(1, n))()
+    if witness:
+        handle = C.c_void_p()
+        ctx.lib.mh_verify_miden_batch_witness.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(MidenVerifyItem), C.POINTER(VerifyResult),
+                                                          C.POINTER(C.c_void_p)]
+        ctx.check(ctx.lib.mh_verify_miden_batch_witness(ctx.h, Ctx.LMCS[hash_fn], n, arr, res, C.byref(handle)))
+        return _results(res, n), _witness_sets(ctx.lib, handle, n)
     ctx.lib.mh_verify_miden_batch.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(MidenVerifyItem), C.POINTER(VerifyResult)]
     ctx.check(ctx.lib.mh_verify_miden_batch(ctx.h, Ctx.LMCS[hash_fn], n, arr, res))
     return _results(res, n)

@@ -28,8 +28,31 @@ struct Plan {
   size_t n_siblings = 0;            // digests the commitment stream must carry, exactly
   std::vector<uint32_t> level_off;  // depth + 1 entries: the parents of level l are pairs [level_off[l], level_off[l + 1])
   std::vector<uint32_t> pairs;      // 2 per parent: left source, right source
+  std::vector<uint64_t> indices;    // the opened indices as build() took them: slot q of level 0 is leaf indices[q]
   size_t n_parents(int l) const { return level_off[l + 1] - level_off[l]; }
+  size_t n_nodes() const { return pairs.size() / 2; }  // derived parents of all levels; level_off[l] places level l's among them
 };
+
+// What reading the opening back as a Merkle witness (mh_lmcs_witness*) needs beside the plan: for every slot of the level below, the
+// parent that consumes it.  The slots of level 0 (the leaves) come first, then level after level the parents of the plan, the root
+// excluded: slot_off(plan, l) + i is slot i of level l, and parent_of[..] is a slot of level l + 1 = a parent of pairs level l.
+// The authentication path of leaf q is then: a = q; per level l: p = parent_of[slot_off(l) + a], the path element is the source of
+// pair level_off[l] + p that is not slot a, a = p.  The node set in `nodes` order is the plan's own: parent level_off[l] + p.
+struct PathTable {
+  std::vector<uint32_t> parent_of;  // n_leaves + n_nodes - 1 entries (depth 0: none)
+};
+inline size_t slot_off(const Plan& pl, int l) { return l == 0 ? 0 : pl.n_leaves + pl.level_off[l - 1]; }
+inline void build_paths(const Plan& pl, PathTable& out) {
+  out.parent_of.assign(pl.depth ? pl.n_leaves + pl.n_nodes() - 1 : 0, 0);
+  for (int l = 0; l < pl.depth; l++) {
+    const size_t s0 = slot_off(pl, l);
+    for (size_t p = 0; p < pl.n_parents(l); p++)
+      for (int side = 0; side < 2; side++) {
+        const uint32_t s = pl.pairs[2 * ((size_t)pl.level_off[l] + p) + side];
+        if (!(s & SIBLING)) out.parent_of[s0 + s] = (uint32_t)p;
+      }
+  }
+}
 
 inline size_t aligned_width(size_t w, size_t alignment) { return (w + alignment - 1) / alignment * alignment; }
 
@@ -45,6 +68,7 @@ inline bool build(int depth, const uint64_t* idx, size_t n, Plan& out, std::stri
   }
   out.depth = depth;
   out.n_leaves = n;
+  out.indices.assign(idx, idx + n);
   out.level_off.reserve((size_t)depth + 1);
   out.level_off.push_back(0);
   std::vector<uint64_t> level(idx, idx + n), up;

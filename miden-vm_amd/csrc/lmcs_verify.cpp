@@ -82,7 +82,102 @@ bool execute_host(int lmcs, const lmcs_plan::Opening& op) {
   return cur.size() == 1 && cur[0] == Digest4{op.root[0], op.root[1], op.root[2], op.root[3]};
 }
 
+bool execute_host_witness(int lmcs, const lmcs_plan::Opening& op, std::vector<u64>& leaf_digests, std::vector<u64>& paths, std::vector<u64>& nodes) {
+  const lmcs_plan::Plan& pl = op.plan;
+  lmcs_plan::PathTable pt;
+  lmcs_plan::build_paths(pl, pt);
+  leaf_digests.resize(4 * pl.n_leaves);
+  paths.resize(4 * pl.n_leaves * (size_t)pl.depth);
+  nodes.resize(4 * pl.n_nodes());
+  for (size_t q = 0; q < pl.n_leaves; q++) {
+    u64 st[lmcs_host::MAX_STATE_WORDS] = {0};
+    const u64* row = op.rows + q * op.row_len;
+    for (uint32_t w : op.hashed) {
+      lmcs_host::leaf_absorb(lmcs, st, row, w);
+      row += w;
+    }
+    for (int i = 0; i < 4; i++) leaf_digests[4 * q + i] = st[i];
+  }
+  std::vector<uint32_t> anc(pl.n_leaves);  // the slot of every leaf's ancestor on the current level
+  for (size_t q = 0; q < pl.n_leaves; q++) anc[q] = (uint32_t)q;
+  const u64* cur = leaf_digests.data();  // the level below: the leaves, then the nodes of the level before
+  for (int l = 0; l < pl.depth; l++) {
+    auto source = [&](uint32_t s) { return (s & lmcs_plan::SIBLING) ? op.sibs + 4 * (size_t)(s & ~lmcs_plan::SIBLING) : cur + 4 * (size_t)s; };
+    const size_t p0 = pl.level_off[l], s0 = lmcs_plan::slot_off(pl, l);
+    for (size_t p = 0; p < pl.n_parents(l); p++) {
+      const u64 *a = source(pl.pairs[2 * (p0 + p)]), *b = source(pl.pairs[2 * (p0 + p) + 1]);
+      const Digest4 d = lmcs_host::compress2(lmcs, Digest4{a[0], a[1], a[2], a[3]}, Digest4{b[0], b[1], b[2], b[3]});
+      for (int i = 0; i < 4; i++) nodes[4 * (p0 + p) + i] = d[i];
+    }
+    for (size_t q = 0; q < pl.n_leaves; q++) {
+      const uint32_t p = pt.parent_of[s0 + anc[q]];
+      const uint32_t ls = pl.pairs[2 * (p0 + p)], rs = pl.pairs[2 * (p0 + p) + 1];
+      const u64* other = source(ls == anc[q] ? rs : ls);
+      for (int i = 0; i < 4; i++) paths[4 * (q * (size_t)pl.depth + l) + i] = other[i];
+      anc[q] = p;
+    }
+    cur = nodes.data() + 4 * p0;
+  }
+  const u64* top = pl.depth ? nodes.data() + 4 * (pl.n_nodes() - 1) : leaf_digests.data();
+  return top[0] == op.root[0] && top[1] == op.root[1] && top[2] == op.root[2] && top[3] == op.root[3];
+}
+
+bool witness_shape(const mh_lmcs_opening& o, lmcs_plan::Plan& plan, std::string& why) {
+  if (!o.indices && o.n_indices) return why = "null array", false;
+  if (o.log_height < 0 || o.log_height > lmcs_plan::MAX_DEPTH) return why = "tree height out of range (0..32)", false;
+  if (o.n_indices < 1) return why = "an opening needs at least one index", false;
+  if (o.n_indices > lmcs_plan::MAX_LEAVES) return why = "too many opened leaves", false;
+  for (size_t i = 0; i < o.n_indices; i++)
+    if (o.indices[i] >> o.log_height) return why = "index " + std::to_string(i) + " outside the tree", false;
+  std::vector<uint64_t> idx(o.indices, o.indices + o.n_indices);
+  std::sort(idx.begin(), idx.end());
+  idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
+  return lmcs_plan::build(o.log_height, idx.data(), idx.size(), plan, why);
+}
+
 }  // namespace lmcs_verify
+
+namespace {
+int reject(char* err, size_t err_cap, int code, const std::string& msg) {
+  if (err && err_cap) snprintf(err, err_cap, "opening rejected: %s", msg.c_str());
+  return code;
+}
+}  // namespace
+
+extern "C" int mh_lmcs_witness_size(const mh_lmcs_opening* o, size_t* n_leaves, size_t* n_nodes, char* err, size_t err_cap) {
+  try {
+    if (!o || !n_leaves || !n_nodes) return reject(err, err_cap, MH_ERR_INVALID, "null argument");
+    lmcs_plan::Plan plan;
+    std::string why;
+    if (!lmcs_verify::witness_shape(*o, plan, why)) return reject(err, err_cap, MH_ERR_INVALID, why);
+    *n_leaves = plan.n_leaves;
+    *n_nodes = plan.n_nodes();
+    if (err && err_cap) err[0] = 0;
+    return MH_OK;
+  } catch (const std::exception& e) {
+    return reject(err, err_cap, MH_ERR_INTERNAL, e.what());
+  }
+}
+
+extern "C" int mh_lmcs_witness(int lmcs, int salt_elems, const mh_lmcs_opening* o, uint64_t* leaf_digests, uint64_t* paths, uint64_t* nodes,
+                               char* err, size_t err_cap) {
+  try {
+    if (!o) return reject(err, err_cap, MH_ERR_INVALID, "null argument");
+    lmcs_plan::Opening op;
+    std::string why;
+    if (!lmcs_verify::prepare(lmcs, salt_elems, *o, op, why)) return reject(err, err_cap, MH_ERR_INVALID, why);
+    if (!leaf_digests || (!paths && op.plan.depth)) return reject(err, err_cap, MH_ERR_INVALID, "null output buffer");
+    std::vector<u64> ld, pa, nd;
+    if (!lmcs_verify::execute_host_witness(lmcs, op, ld, pa, nd)) return reject(err, err_cap, MH_ERR_INVALID, "Merkle root mismatch");
+    std::copy(ld.begin(), ld.end(), leaf_digests);
+    std::copy(pa.begin(), pa.end(), paths);
+    if (nodes) std::copy(nd.begin(), nd.end(), nodes);
+    if (err && err_cap) err[0] = 0;
+    return MH_OK;
+  } catch (const std::exception& e) {
+    return reject(err, err_cap, MH_ERR_INTERNAL, e.what());
+  }
+}
 
 extern "C" int mh_lmcs_verify(int lmcs, int salt_elems, const mh_lmcs_opening* o, char* err, size_t err_cap) {
   auto fail = [&](int code, const std::string& msg) {

@@ -20,6 +20,7 @@
 #include "gl.cuh"
 #include "air.hpp"
 #include "kernels.hpp"
+#include "lmcs_verify.hpp"
 #include "poseidon2.cuh"
 #include <cstring>
 #include <memory>
@@ -305,13 +306,20 @@ int mh_verify_miden(int hash_fn, const uint64_t* public_values, const uint64_t* 
 
 // mh_verify_miden for n proofs through mh_verify_batch (verify_batch.hip): the statement layer per item exactly as above, the openings of
 // all of them hashed on the device in one pass.  An item mh_verify_miden refuses before it reads the proof is refused here the same way.
-int mh_verify_miden_batch(mh_ctx* ctx, int hash_fn, size_t n, const mh_miden_verify_item* items, mh_verify_result* results) {
+static int verify_miden_batch(mh_ctx* ctx, int hash_fn, size_t n, const mh_miden_verify_item* items, mh_verify_result* results,
+                              mh_witness_set** set_out) {
   if (!ctx) return MH_ERR_INVALID;
+  std::unique_ptr<mh_witness_set> set(set_out ? new mh_witness_set : nullptr);
+  if (set) set->items.resize(n);
+  auto done = [&]() {
+    if (set_out) *set_out = set.release();
+    return MH_OK;
+  };
   if (n && (!items || !results)) {
     ctx->err = "mh_verify_miden_batch: null argument";
     return MH_ERR_INVALID;
   }
-  if (!n) return MH_OK;
+  if (!n) return done();
   mh_pcs_params prm;
   mh_miden_pcs_params(&prm);
   u64 state[12];
@@ -357,15 +365,38 @@ int mh_verify_miden_batch(mh_ctx* ctx, int hash_fn, size_t n, const mh_miden_ver
     batch.push_back(v);
     who.push_back(i);
   }
-  if (batch.empty()) return MH_OK;
+  if (batch.empty()) return done();
   const Blobs& b = blobs();
   const uint64_t* blob_ptr[3] = {b.dag[0].data(), b.dag[1].data(), b.dag[2].data()};
   const size_t blob_len[3] = {b.dag[0].size(), b.dag[1].size(), b.dag[2].size()};
   std::vector<mh_verify_result> out(batch.size());
-  const int rc = mh_verify_batch(ctx, hash_fn, 0, &prm, 3, blob_ptr, blob_len, state, external_cb, batch.size(), batch.data(), out.data());
+  mh_witness_set* got = nullptr;
+  const int rc = set_out ? mh_verify_batch_witness(ctx, hash_fn, 0, &prm, 3, blob_ptr, blob_len, state, external_cb, batch.size(), batch.data(),
+                                                   out.data(), &got)
+                         : mh_verify_batch(ctx, hash_fn, 0, &prm, 3, blob_ptr, blob_len, state, external_cb, batch.size(), batch.data(), out.data());
   if (rc != MH_OK) return rc;
   for (size_t k = 0; k < batch.size(); k++) results[who[k]] = out[k];
-  return MH_OK;
+  if (got) {  // the batch numbered the items it was given: back to the caller's numbering
+    for (size_t k = 0; k < batch.size(); k++) set->items[who[k]] = std::move(got->items[k]);
+    set->blocks = std::move(got->blocks);
+    mh_witness_set_free(got);
+  }
+  return done();
+}
+
+int mh_verify_miden_batch(mh_ctx* ctx, int hash_fn, size_t n, const mh_miden_verify_item* items, mh_verify_result* results) {
+  return verify_miden_batch(ctx, hash_fn, n, items, results, nullptr);
+}
+
+int mh_verify_miden_batch_witness(mh_ctx* ctx, int hash_fn, size_t n, const mh_miden_verify_item* items, mh_verify_result* results,
+                                  mh_witness_set** out) {
+  if (!ctx) return MH_ERR_INVALID;
+  if (!out) {
+    ctx->err = "mh_verify_miden_batch_witness: null argument";
+    return MH_ERR_INVALID;
+  }
+  *out = nullptr;
+  return verify_miden_batch(ctx, hash_fn, n, items, results, out);
 }
 
 // ExecutionTrace::check_constraints (processor/src/trace/mod.rs:261-278) of this statement: check.hip with the statement's challenger state,

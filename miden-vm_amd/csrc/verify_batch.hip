@@ -11,8 +11,11 @@
 //                     over the plan's (left, right) pairs, take each digest from the LDS array of the level below or from the sibling
 //                     buffer, compress, and write the other LDS array; a barrier between levels; the last digest against the root,
 //                     one lane stores the 0/1 verdict.  LDS = 2 x (largest opening of the launch) x 32 B, at most 2 x 1024 x 32 B.
-// H = the five configurations (MH_LMCS_*).  One read-back of the verdicts ends a pass; nothing synchronises per proof.  Device memory
-// per pass is bounded by MH_VERIFY_BATCH_BYTES (default 256 MB): larger batches run as consecutive chunks.
+//   k_vfy_witness<H>  k_vfy_paths that keeps what it derives (mh_lmcs_witness_batch, mh_verify_batch_witness): every
+//                     parent also goes to a pass-wide node array, every opened leaf copies its path element of the level.
+// H = the five configurations (MH_LMCS_*).  One read-back of the verdicts (a witness pass: of leaf digests, nodes, paths and verdicts
+// in one block) ends a pass; nothing synchronises per proof.  Device memory per pass is bounded by MH_VERIFY_BATCH_BYTES (default
+// 256 MB): larger batches run as consecutive chunks.
 #include "ctx.hpp"
 #include "../../include/midenhip.h"
 #include "kernels.hpp"
@@ -30,6 +33,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <thread>
 
 namespace {
@@ -232,6 +236,108 @@ __global__ __launch_bounds__(VB_THREADS) void k_vfy_paths(VbPathArgs a) {
     a.ok[blockIdx.x] = (cur[0] == op.root[0] && cur[1] == op.root[1] && cur[2] == op.root[2] && cur[3] == op.root[3]) ? 1 : 0;
 }
 
+// The witness form of k_vfy_paths (mh_lmcs_witness_batch): the same walk, and what it derives is kept.  Per level
+// every computed parent goes to the pass-wide `nodes` array (plan order: parent p of the opening is node pair0 + p) as well as to LDS,
+// and every opened leaf q follows its ancestor slot through parent_of (lmcs_plan::PathTable) and copies the OTHER source of its
+// parent's pair -- an LDS slot of the level below or a streamed sibling -- to paths[q][l].  Both read the array of the level below and
+// write elsewhere, so the level's one barrier serves both.  At most 1024 leaves on 256 lanes: four ancestor slots per lane, in
+// registers.  Global writes are 16-byte vector stores.
+struct VbWitOpening {  // 16 bytes
+  u64 path0;  // first digest of this opening in `paths` (n_leaves x depth digests per opening)
+  u32 par0;   // first of its parent_of entries
+  u32 pad;
+};
+struct VbWitArgs {
+  const VbWitOpening* wops;
+  const u32* parent_of;
+  u64* nodes;  // [parents of the pass][4]
+  u64* paths;
+};
+static_assert(VB_MAX_LEAVES == 4 * VB_THREADS, "k_vfy_witness keeps four ancestor slots per lane");
+
+template <int H>
+__global__ __launch_bounds__(VB_THREADS) void k_vfy_witness(VbPathArgs a, VbWitArgs w) {
+  extern __shared__ __attribute__((aligned(16))) u64 vb_lds[];  // two arrays of lds_slots digests
+  const VbOpening op = a.ops[blockIdx.x];
+  const VbWitOpening wo = w.wops[blockIdx.x];
+  u64* cur = vb_lds;
+  u64* nxt = vb_lds + 4 * (size_t)a.lds_slots;
+  for (u32 q = threadIdx.x; q < op.n_leaves; q += VB_THREADS) {
+    const ulonglong2* s = reinterpret_cast<const ulonglong2*>(a.digests + 4 * (size_t)(op.leaf0 + q));
+    ulonglong2* t = reinterpret_cast<ulonglong2*>(cur + 4 * q);
+    t[0] = s[0];
+    t[1] = s[1];
+  }
+  __syncthreads();
+  const u32* lvl = a.lvl + op.lvl0;
+  const u64* sibs = a.sibs + 4 * op.sib0;
+  const u32* par = w.parent_of + wo.par0;  // the slots of the current level: n_slots entries
+  u32 n_slots = op.n_leaves;
+  u32 anc[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) anc[j] = threadIdx.x + j * VB_THREADS;
+#pragma unroll 1
+  for (u32 l = 0; l < op.depth; l++) {
+    const u32 p0 = lvl[l], p1 = lvl[l + 1];
+#pragma unroll 1
+    for (u32 p = p0 + threadIdx.x; p < p1; p += VB_THREADS) {
+      const u32 ls = a.pairs[2 * (size_t)(op.pair0 + p)], rs = a.pairs[2 * (size_t)(op.pair0 + p) + 1];
+      const u64* lp = (ls & lmcs_plan::SIBLING) ? sibs + 4 * (size_t)(ls & ~lmcs_plan::SIBLING) : cur + 4 * ls;
+      const u64* rp = (rs & lmcs_plan::SIBLING) ? sibs + 4 * (size_t)(rs & ~lmcs_plan::SIBLING) : cur + 4 * rs;
+      u64 L[4], R[4], O[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        L[i] = lp[i];
+        R[i] = rp[i];
+      }
+      vb_compress<H>(L, R, O);
+#pragma unroll
+      for (int i = 0; i < 4; i++) nxt[4 * (p - p0) + i] = O[i];
+      ulonglong2* g = reinterpret_cast<ulonglong2*>(w.nodes + 4 * (size_t)(op.pair0 + p));
+      g[0] = make_ulonglong2(O[0], O[1]);
+      g[1] = make_ulonglong2(O[2], O[3]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const u32 q = threadIdx.x + j * VB_THREADS;
+      if (q < op.n_leaves) {
+        const u32 pr = par[anc[j]];
+        const size_t e = 2 * (size_t)(op.pair0 + p0 + pr);
+        const u32 ls = a.pairs[e], rs = a.pairs[e + 1];
+        const u32 o = ls == anc[j] ? rs : ls;
+        const u64* src = (o & lmcs_plan::SIBLING) ? sibs + 4 * (size_t)(o & ~lmcs_plan::SIBLING) : cur + 4 * o;
+        ulonglong2* g = reinterpret_cast<ulonglong2*>(w.paths + 4 * (wo.path0 + (size_t)q * op.depth + l));
+        g[0] = make_ulonglong2(src[0], src[1]);
+        g[1] = make_ulonglong2(src[2], src[3]);
+        anc[j] = pr;
+      }
+    }
+    par += n_slots;
+    n_slots = p1 - p0;
+    __syncthreads();
+    u64* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  if (threadIdx.x == 0)
+    a.ok[blockIdx.x] = (cur[0] == op.root[0] && cur[1] == op.root[1] && cur[2] == op.root[2] && cur[3] == op.root[3]) ? 1 : 0;
+}
+
+template <int H>
+void launch_witness(mh_ctx* c, unsigned blocks, size_t lds, const VbPathArgs& a, const VbWitArgs& w) {
+  MH_LAUNCH(k_vfy_witness<H>, dim3(blocks), dim3(VB_THREADS), lds, c->stream, a, w);
+}
+void dispatch_witness(mh_ctx* c, int lmcs, unsigned blocks, size_t lds, const VbPathArgs& a, const VbWitArgs& w) {
+  switch (lmcs) {
+    case MH_LMCS_POSEIDON2: return launch_witness<MH_LMCS_POSEIDON2>(c, blocks, lds, a, w);
+    case MH_LMCS_BLAKE3: return launch_witness<MH_LMCS_BLAKE3>(c, blocks, lds, a, w);
+    case MH_LMCS_KECCAK: return launch_witness<MH_LMCS_KECCAK>(c, blocks, lds, a, w);
+    case MH_LMCS_RPO: return launch_witness<MH_LMCS_RPO>(c, blocks, lds, a, w);
+    case MH_LMCS_RPX: return launch_witness<MH_LMCS_RPX>(c, blocks, lds, a, w);
+    default: throw MhError(MH_ERR_INTERNAL, "no witness kernel for this LMCS id");
+  }
+}
+
 template <int H>
 void launch_leaves(mh_ctx* c, unsigned blocks, const VbLeafArgs& a, const VbClasses& ct) {
   MH_LAUNCH(k_vfy_leaves<H>, dim3(blocks), dim3(VB_THREADS), 0, c->stream, a, ct);
@@ -277,6 +383,10 @@ size_t pass_bytes(const Opening& op) {  // device memory one opening takes in a 
   return 8 * op.plan.n_leaves * op.row_len + 32 * op.plan.n_siblings + 32 * op.plan.n_leaves + 4 * op.plan.pairs.size() +
          4 * op.plan.level_off.size() + sizeof(VbOpening) + 12 * lanes + 4;
 }
+size_t witness_bytes(const Opening& op) {  // ... and what a witness pass adds: nodes, paths, parent_of, its descriptor
+  const size_t n_par = op.plan.depth ? op.plan.n_leaves + op.plan.n_nodes() - 1 : 0;
+  return 32 * op.plan.n_nodes() + 32 * op.plan.n_leaves * (size_t)op.plan.depth + 4 * n_par + sizeof(VbWitOpening);
+}
 size_t batch_bytes_limit() {
   const char* e = getenv("MH_VERIFY_BATCH_BYTES");
   if (e && *e) {
@@ -296,12 +406,23 @@ struct Upload {
   }
 };
 
-// one pass: ops[first .. last) hashed and compared; ok[i - first] = verdict
-void run_pass(mh_ctx* c, int lmcs, const std::vector<const Opening*>& ops, size_t first, size_t last, int* ok) {
+// Where a witness pass leaves its arrays, per opening of ops: in the caller's buffers (`outs`: mh_lmcs_witness_batch), or where they
+// landed -- the read-back block of the pass is kept whole in `blocks` and where[i] points into it (mh_verify_batch_witness).
+struct WitnessDst {
+  const mh_lmcs_witness_out* outs = nullptr;
+  std::vector<std::unique_ptr<u64[]>>* blocks = nullptr;
+  std::vector<mh_lmcs_witness_out>* where = nullptr;
+};
+
+// one pass: ops[first .. last) hashed and compared; ok[i - first] = verdict.  With outs (or null) the pass runs the witness kernel, and
+// one read-back brings verdicts, leaf digests, paths and nodes.
+void run_pass(mh_ctx* c, int lmcs, const std::vector<const Opening*>& ops, size_t first, size_t last, int* ok, const WitnessDst* outs) {
   const size_t n = last - first;
   std::vector<u64> fields, sibs, row_off;
-  std::vector<u32> out_slot, pairs, lvl;
+  std::vector<u32> out_slot, pairs, lvl, parent_of;
   std::vector<VbOpening> desc(n);
+  std::vector<VbWitOpening> wdesc(outs ? n : 0);
+  size_t n_paths = 0;
   std::map<std::vector<u32>, std::vector<size_t>> classes;  // widths -> openings of the pass
   std::vector<size_t> field0(n);
   size_t n_leaves = 0, n_fields = 0, n_sibs = 0, n_pairs = 0, n_lvl = 0;
@@ -340,6 +461,13 @@ void run_pass(mh_ctx* c, int lmcs, const std::vector<const Opening*>& ops, size_
     leaf0 += d.n_leaves;
     max_leaves = std::max(max_leaves, d.n_leaves);
     classes[op.hashed].push_back(i);
+    if (outs) {
+      lmcs_plan::PathTable pt;
+      lmcs_plan::build_paths(op.plan, pt);
+      wdesc[i] = VbWitOpening{(u64)n_paths, (u32)parent_of.size(), 0};
+      parent_of.insert(parent_of.end(), pt.parent_of.begin(), pt.parent_of.end());
+      n_paths += op.plan.n_leaves * (size_t)op.plan.depth;
+    }
   }
   // lanes: class after class, each padded to whole waves; launches of at most VB_MAX_CLASSES classes / VB_MAX_WIDTHS widths
   struct Launch {
@@ -382,8 +510,10 @@ void run_pass(mh_ctx* c, int lmcs, const std::vector<const Opening*>& ops, size_
     }
     flush();
   }
-  Upload u_fields, u_sibs, u_rows, u_slots, u_pairs, u_lvl, u_desc;
-  DevBuf digests(32 * (size_t)n_leaves), d_ok(4 * n);
+  Upload u_fields, u_sibs, u_rows, u_slots, u_pairs, u_lvl, u_desc, u_par, u_wdesc;
+  // a witness pass reads back one buffer: [leaf digests | nodes | paths | verdicts]
+  const size_t n_nodes = n_pairs / 2, back_words = 4 * (n_leaves + n_nodes + n_paths) + (n + 1) / 2;
+  DevBuf digests(outs ? 8 * back_words : 32 * (size_t)n_leaves), d_ok(outs ? 16 : 4 * n);
   VbLeafArgs la{};
   VbPathArgs pa{};
   {
@@ -395,6 +525,13 @@ void run_pass(mh_ctx* c, int lmcs, const std::vector<const Opening*>& ops, size_
     pa.pairs = u_pairs.put(c, pairs);
     pa.lvl = u_lvl.put(c, lvl);
     pa.ops = u_desc.put(c, desc);
+  }
+  VbWitArgs wa{};
+  if (outs) {
+    wa.parent_of = u_par.put(c, parent_of);
+    wa.wops = u_wdesc.put(c, wdesc);
+    wa.nodes = digests.u() + 4 * n_leaves;
+    wa.paths = wa.nodes + 4 * n_nodes;
   }
   la.digests = digests.u();
   {
@@ -408,23 +545,55 @@ void run_pass(mh_ctx* c, int lmcs, const std::vector<const Opening*>& ops, size_
     }
   }
   pa.digests = digests.u();
-  pa.ok = (int*)d_ok.p;
+  pa.ok = outs ? (int*)(wa.paths + 4 * n_paths) : (int*)d_ok.p;
   pa.lds_slots = max_leaves;
-  {
-    ProfScope ps(c, "vfy_paths");
-    dispatch_paths(c, lmcs, (unsigned)n, 2 * 32 * (size_t)max_leaves, pa);
+  if (!outs) {
+    {
+      ProfScope ps(c, "vfy_paths");
+      dispatch_paths(c, lmcs, (unsigned)n, 2 * 32 * (size_t)max_leaves, pa);
+    }
+    c->d2h(ok, d_ok.p, 4 * n);  // the one read-back (waits for the stream: the host vectors above may go)
+    return;
   }
-  c->d2h(ok, d_ok.p, 4 * n);  // the one read-back (waits for the stream: the host vectors above may go)
+  {
+    ProfScope ps(c, "vfy_witness");
+    dispatch_witness(c, lmcs, (unsigned)n, 2 * 32 * (size_t)max_leaves, pa, wa);
+  }
+  std::unique_ptr<u64[]> back(new u64[back_words]);  // not zero-filled: every word is read back
+  {
+    ProfScope ps(c, "vfy_readback", 8.0 * back_words);
+    c->d2h(back.get(), digests.p, 8 * back_words);  // the one read-back
+  }
+  memcpy(ok, back.get() + 4 * (n_leaves + n_nodes + n_paths), 4 * n);
+  // a rejected opening's arrays are dropped here: its buffers stay as the caller left them
+  for (size_t i = 0; i < n; i++) {
+    if (!ok[i]) continue;
+    const Opening& op = *ops[first + i];
+    u64* leaf = back.get() + 4 * (size_t)desc[i].leaf0;
+    u64* path = back.get() + 4 * (n_leaves + n_nodes + (size_t)wdesc[i].path0);
+    u64* node = back.get() + 4 * (n_leaves + (size_t)desc[i].pair0);
+    if (outs->where) {
+      (*outs->where)[first + i] = mh_lmcs_witness_out{leaf, path, node};
+      continue;
+    }
+    const mh_lmcs_witness_out& o = outs->outs[first + i];
+    const size_t k = op.plan.n_leaves;
+    memcpy(o.leaf_digests, leaf, 32 * k);
+    if (op.plan.depth) memcpy(o.paths, path, 32 * k * (size_t)op.plan.depth);
+    if (o.nodes && op.plan.depth) memcpy(o.nodes, node, 32 * op.plan.n_nodes());
+  }
+  if (outs->blocks) outs->blocks->push_back(std::move(back));
 }
 
 // every opening of ops (all within the kernels' bounds) on the device, in passes of at most MH_VERIFY_BATCH_BYTES
-void run_device(mh_ctx* c, int lmcs, const std::vector<const Opening*>& ops, std::vector<int>& ok) {
+void run_device(mh_ctx* c, int lmcs, const std::vector<const Opening*>& ops, std::vector<int>& ok, const WitnessDst* outs = nullptr) {
   ok.assign(ops.size(), 0);
   const size_t limit = batch_bytes_limit();
+  auto cost = [&](const Opening& op) { return pass_bytes(op) + (outs ? witness_bytes(op) : 0); };
   for (size_t first = 0; first < ops.size();) {
     size_t last = first, bytes = 0;
-    while (last < ops.size() && (last == first || bytes + pass_bytes(*ops[last]) <= limit)) bytes += pass_bytes(*ops[last++]);
-    run_pass(c, lmcs, ops, first, last, ok.data() + first);
+    while (last < ops.size() && (last == first || bytes + cost(*ops[last]) <= limit)) bytes += cost(*ops[last++]);
+    run_pass(c, lmcs, ops, first, last, ok.data() + first, outs);
     first = last;
   }
 }
@@ -480,9 +649,42 @@ int mh_lmcs_verify_batch(mh_ctx* c, int lmcs, int salt_elems, size_t n, const mh
   VB_CATCH
 }
 
-int mh_verify_batch(mh_ctx* c, int lmcs, int salt_elems, const mh_pcs_params* params, int n_airs, const uint64_t* const* air_blobs,
-                    const size_t* air_blob_words, const uint64_t challenger_state[12], mh_external_assertions external, size_t n_items,
-                    const mh_verify_item* items, mh_verify_result* results) {
+int mh_lmcs_witness_batch(mh_ctx* c, int lmcs, int salt_elems, size_t n, const mh_lmcs_opening* items, const mh_lmcs_witness_out* outs, int* ok) {
+  VB_TRY(c)
+  MH_REQUIRE(c, "null context");
+  MH_REQUIRE((items && outs && ok) || !n, "null argument");
+  MH_REQUIRE(lmcs >= MH_LMCS_POSEIDON2 && lmcs <= MH_LMCS_RPX, "unknown LMCS hasher id");
+  MH_REQUIRE(salt_elems >= 0 && salt_elems <= MH_MAX_SALT_ELEMS, "salt_elems must be in 0..MH_MAX_SALT_ELEMS");
+  if (!n) return MH_OK;
+  std::vector<Opening> prepared(n);
+  std::vector<const Opening*> ops;
+  std::vector<mh_lmcs_witness_out> dst;
+  std::vector<size_t> who;
+  for (size_t i = 0; i < n; i++) {
+    std::string why;
+    ok[i] = 0;
+    if (!lmcs_verify::prepare(lmcs, salt_elems, items[i], prepared[i], why)) continue;  // refused on the host: verdict 0, buffers untouched
+    const std::string bound = device_bounds(prepared[i]);
+    MH_REQUIRE(bound.empty(), "mh_lmcs_witness_batch: opening " + std::to_string(i) + " has " + bound + ": use mh_lmcs_witness");
+    MH_REQUIRE(outs[i].leaf_digests && (outs[i].paths || !prepared[i].plan.depth), "mh_lmcs_witness_batch: null output buffer");
+    ops.push_back(&prepared[i]);
+    dst.push_back(outs[i]);
+    who.push_back(i);
+  }
+  if (ops.empty()) return MH_OK;
+  HIP_CHECK(hipSetDevice(c->device));
+  std::vector<int> verdict;
+  WitnessDst w;
+  w.outs = dst.data();
+  run_device(c, lmcs, ops, verdict, &w);
+  for (size_t k = 0; k < ops.size(); k++) ok[who[k]] = verdict[k];
+  VB_CATCH
+}
+
+// mh_verify_batch, and with `out` mh_verify_batch_witness: the same replay and the same verdicts, the device pass in its witness form
+static int verify_batch_impl(mh_ctx* c, int lmcs, int salt_elems, const mh_pcs_params* params, int n_airs, const uint64_t* const* air_blobs,
+                             const size_t* air_blob_words, const uint64_t challenger_state[12], mh_external_assertions external, size_t n_items,
+                             const mh_verify_item* items, mh_verify_result* results, mh_witness_set** out) {
   VB_TRY(c)
   MH_REQUIRE(c, "null context");
   MH_REQUIRE(params && air_blobs && air_blob_words && challenger_state, "null argument");
@@ -490,7 +692,11 @@ int mh_verify_batch(mh_ctx* c, int lmcs, int salt_elems, const mh_pcs_params* pa
   MH_REQUIRE(n_airs > 0 && n_airs <= 256, "need between 1 and 256 AIR instances");
   MH_REQUIRE(lmcs >= MH_LMCS_POSEIDON2 && lmcs <= MH_LMCS_RPX, "unknown LMCS hasher id");
   MH_REQUIRE(salt_elems >= 0 && salt_elems <= MH_MAX_SALT_ELEMS, "salt_elems must be in 0..MH_MAX_SALT_ELEMS");
-  if (!n_items) return MH_OK;
+  std::unique_ptr<mh_witness_set> set(out ? new mh_witness_set : nullptr);
+  if (!n_items) {
+    if (out) *out = set.release();
+    return MH_OK;
+  }
   std::vector<DagIR> airs;
   for (int i = 0; i < n_airs; i++) airs.push_back(dag_parse(air_blobs[i], air_blob_words[i]));
   struct Replay {
@@ -544,9 +750,15 @@ int mh_verify_batch(mh_ctx* c, int lmcs, int salt_elems, const mh_pcs_params* pa
       who.push_back({i, k});
     }
   std::vector<int> verdict;
+  std::vector<mh_lmcs_witness_out> where(out ? ops.size() : 0);  // an accepted opening's arrays, in the set's read-back blocks
+  WitnessDst w;
+  if (out) {
+    w.blocks = &set->blocks;
+    w.where = &where;
+  }
   if (!ops.empty()) {
     HIP_CHECK(hipSetDevice(c->device));
-    run_device(c, lmcs, ops, verdict);
+    run_device(c, lmcs, ops, verdict, out ? &w : nullptr);
   }
   for (size_t k = ops.size(); k-- > 0;)  // backwards: the first failed opening of an item names it
     if (!verdict[k]) {
@@ -561,7 +773,73 @@ int mh_verify_batch(mh_ctx* c, int lmcs, int salt_elems, const mh_pcs_params* pa
     for (int k = 0; k < 4; k++) o.digest[k] = good ? rp[i].digest[k] : 0;
     snprintf(o.reason, sizeof o.reason, "%s", good ? "" : rp[i].reason.c_str());
   }
+  if (out) {  // an accepted item's openings, in the order the replay met them = proof order
+    set->items.resize(n_items);
+    for (size_t k = 0; k < ops.size(); k++) {
+      const Replay& r = rp[who[k].first];
+      if (r.code != MH_OK) continue;
+      const Opening& op = *ops[k];
+      mh_witness_set::Tree t;
+      int num = 0;
+      if (sscanf(r.labels[who[k].second].c_str(), "committed tree %d of", &num) == 1) t.kind = 0;
+      else if (sscanf(r.labels[who[k].second].c_str(), "FRI round %d tree", &num) == 1) t.kind = 1;
+      else throw MhError(MH_ERR_INTERNAL, "verify batch: an opening of an unnamed tree");
+      t.which = num;
+      t.depth = op.plan.depth;
+      t.row_len = op.row_len;
+      for (int j = 0; j < 4; j++) t.root[j] = op.root[j];
+      t.indices = op.plan.indices;
+      t.rows.assign(op.rows, op.rows + op.plan.n_leaves * op.row_len);
+      t.n_nodes = op.plan.n_nodes();
+      t.leaf_digests = where[k].leaf_digests;
+      t.paths = where[k].paths;
+      t.nodes = where[k].nodes;
+      set->items[who[k].first].push_back(std::move(t));
+    }
+    *out = set.release();
+  }
   VB_CATCH
 }
+
+int mh_verify_batch(mh_ctx* c, int lmcs, int salt_elems, const mh_pcs_params* params, int n_airs, const uint64_t* const* air_blobs,
+                    const size_t* air_blob_words, const uint64_t challenger_state[12], mh_external_assertions external, size_t n_items,
+                    const mh_verify_item* items, mh_verify_result* results) {
+  return verify_batch_impl(c, lmcs, salt_elems, params, n_airs, air_blobs, air_blob_words, challenger_state, external, n_items, items, results,
+                           nullptr);
+}
+
+int mh_verify_batch_witness(mh_ctx* c, int lmcs, int salt_elems, const mh_pcs_params* params, int n_airs, const uint64_t* const* air_blobs,
+                            const size_t* air_blob_words, const uint64_t challenger_state[12], mh_external_assertions external, size_t n_items,
+                            const mh_verify_item* items, mh_verify_result* results, mh_witness_set** out) {
+  if (!out) {
+    if (c) c->err = "mh_verify_batch_witness: null argument";
+    return MH_ERR_INVALID;
+  }
+  *out = nullptr;
+  return verify_batch_impl(c, lmcs, salt_elems, params, n_airs, air_blobs, air_blob_words, challenger_state, external, n_items, items, results,
+                           out);
+}
+
+size_t mh_witness_set_trees(const mh_witness_set* set, size_t item) { return set && item < set->items.size() ? set->items[item].size() : 0; }
+
+int mh_witness_set_tree(const mh_witness_set* set, size_t item, size_t t, mh_witness_tree* view) {
+  if (!set || !view || item >= set->items.size() || t >= set->items[item].size()) return MH_ERR_INVALID;
+  const mh_witness_set::Tree& w = set->items[item][t];
+  view->kind = w.kind;
+  view->which = w.which;
+  view->depth = w.depth;
+  view->n_leaves = w.indices.size();
+  view->n_nodes = w.n_nodes;
+  view->row_len = w.row_len;
+  for (int j = 0; j < 4; j++) view->root[j] = w.root[j];
+  view->indices = w.indices.data();
+  view->rows = w.rows.data();
+  view->leaf_digests = w.leaf_digests;
+  view->paths = w.paths;
+  view->nodes = w.nodes;
+  return MH_OK;
+}
+
+void mh_witness_set_free(mh_witness_set* set) { delete set; }
 
 }  // extern "C"
