@@ -33,6 +33,17 @@ pub struct mh_check_entry {
 /// mh_balance_entry.first_push: the push list was not collected (more than 2^22 pushes).
 pub const MH_BALANCE_NO_PUSHES: u64 = u64::MAX;
 
+/// mh_fill_multiplicities*: fraction `fraction` of LogUp column `lookup_column` of instance `instance` has a multiplicity that is
+/// affine in main-trace column `main_column`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_mult_slot {
+    pub instance: i32,
+    pub lookup_column: u32,
+    pub fraction: u32,
+    pub main_column: u32,
+}
+
 /// An encoded denominator whose net multiplicity is not zero (mh_check_balance*; the reference's `Unmatched`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -404,4 +415,8 @@ unsafe extern "C" {
     pub fn mh_check_balance_miden_traces(ctx: *mut mh_ctx, m: *const mh_miden, traces: *const *mut mh_trace, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, flags: c_int, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
     pub fn mh_check_balance_precompile(ctx: *mut mh_ctx, s: *mut mh_precompile, mains_rowmajor: *const *const u64, log_heights: *const c_int, public_root: *const u64, flags: c_int, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
     pub fn mh_check_balance_precompile_traces(ctx: *mut mh_ctx, s: *mut mh_precompile, traces: *const *mut mh_trace, public_root: *const u64, flags: c_int, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
+    // multiplicity columns filled on the device, in place (csrc/multiplicity.hip); the report is mh_check_balance's exact stage
+    pub fn mh_fill_multiplicities(ctx: *mut mh_ctx, n: c_int, lookups: *const *const mh_lookup, traces: *const *mut mh_trace, preprocessed: *const *const mh_trace, randomness: *const u64, n_randomness: usize, boundary_denoms: *const u64, boundary_signs: *const i32, n_boundary: usize, slots: *const mh_mult_slot, n_slots: usize, n_written: *mut u64, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
+    pub fn mh_fill_multiplicities_miden_traces(ctx: *mut mh_ctx, m: *const mh_miden, traces: *const *mut mh_trace, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, slots: *const mh_mult_slot, n_slots: usize, n_written: *mut u64, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
+    pub fn mh_fill_multiplicities_precompile_traces(ctx: *mut mh_ctx, s: *mut mh_precompile, traces: *const *mut mh_trace, public_root: *const u64, slots: *const mh_mult_slot, n_slots: usize, n_written: *mut u64, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
 }

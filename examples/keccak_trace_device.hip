@@ -6,7 +6,8 @@
 //
 // The chiplet is a three-address machine `c = ROL(a OP b, s)`: one wave runs the 3200 program rows of ONE permutation (address space in
 // LDS), lane c writes column c of its 34-column band and counts the byte-pair / Range16 requests of every active row into the table's
-// multiplicity matrix (64-bit atomics in HBM).  The
+// multiplicity matrix (64-bit atomics in HBM).  (These hand-rolled counts can now come from the library instead: build the table's
+// trace with its three columns unset and call mh_fill_multiplicities_precompile_traces before proving.)  The
 // 128-slot round program (op, rotation, back-offsets, provide multiplicity) is passed in by the caller: the kernel is the machine,
 // not the Keccak schedule.
 //

@@ -909,6 +909,54 @@ int mh_check_balance_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_trace* 
                                        const uint64_t public_root[4], int flags, mh_balance_entry* entries, size_t entry_cap,
                                        size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);
 
+/* ---- multiplicity columns: the provider side of a table-style LogUp bus, counted on the device ---------------------------------------
+ * Replaces the host-side ledgers the reference keeps next to its trace generators (precompiles-prover byte_pair_lut.rs:134-226,
+ * uint/add/trace.rs:37-103 UintAddRequires, RangeChecker::emit_table_rows).  A multiplicity cell is the value that makes its key's net
+ * zero; the lookup programs say who pushes what.  Inputs as mh_check_balance, plus the SLOTS: the fractions whose multiplicity is
+ * affine in a main-trace column, m(r) = a(r) + b(r) * trace[r][main_column].  Device stage: csrc/multiplicity.hip.
+ *   probe    every program of an instance with declared columns is evaluated on a scratch copy of its trace with all declared columns
+ *            0 and again with all 1: a = m at 0, b = (m at 1) - (m at 0), key = d.  The declaration is checked numerically and
+ *            refused (MH_ERR_INVALID, mh_last_error names instance / column / fraction) when a slot's denominator differs between
+ *            the two evaluations, when a slot's b is not a base-field value, when a fraction that is no slot differs between them (an
+ *            undeclared reader of a declared column), when a slot indexes outside its program or trace, when two slots name the same
+ *            (instance, lookup_column, fraction), or when a live push has a zero denominator.  A refused call leaves the traces as
+ *            they were.
+ *   net      one table for the statement: every push with a != 0 (other fractions: their m), every boundary push, and every slot
+ *            push with b(r) != 0 -- a provider candidate, also when its a is 0.  Per key: net = sum of a mod p; owner = the candidate
+ *            with the lowest push id (instance base + row * K + fraction, the numbering of mh_check_balance).
+ *   resolve  per cell (instance, declared column, row): the first slot of that column in declaration order with b(r) != 0 decides.
+ *            Its push owns its key: the cell becomes -net[0] / b(r) mod p, canonical.  It does not: 0.  No such slot on the row: the
+ *            cell keeps its value.  *n_written = the cells written.
+ *   verify   the exact stage of mh_check_balance over the filled traces; entries / pushes / totals / caps / ordering are that call's.
+ * MH_OK: every bus balances.  MH_ERR_UNSATISFIED: not (a looked-up value no provider row carries; a cell shared by fractions that
+ * disagree, such as a multiplicity constant over a cycle of rows; a gated provider nobody covers): the report says where, and the
+ * traces stay filled as far as they could be.  n_slots == 0 is mh_check_balance with MH_CHECK_EXACT.  Two calls on the same inputs
+ * leave the same bytes in the traces and return the same report.
+ * The traces are filled IN PLACE in their device storage: fill before the trace is committed or proved (a tree committed earlier
+ * does not follow).  The call orders itself after a pending mh_trace_upload_async and runs on the context's stream.
+ * Not in scope: multiplicities coupled across rows, sharded contexts, host matrices (upload, fill, mh_trace_download). */
+typedef struct mh_mult_slot {   /* fraction `fraction` of LogUp column `lookup_column` of instance `instance` has a multiplicity that
+                                   is affine in main-trace column `main_column` */
+  int32_t instance;
+  uint32_t lookup_column, fraction;   /* as in mh_balance_push */
+  uint32_t main_column;
+} mh_mult_slot;
+int mh_fill_multiplicities(mh_ctx* ctx, int n, const mh_lookup* const* lookups, mh_trace* const* traces,
+                           const mh_trace* const* preprocessed /* or NULL */, const uint64_t* randomness /* EF pairs */, size_t n_randomness,
+                           const uint64_t* boundary_denoms /* EF pairs */, const int32_t* boundary_signs, size_t n_boundary,
+                           const mh_mult_slot* slots, size_t n_slots, uint64_t* n_written, mh_balance_entry* entries, size_t entry_cap,
+                           size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);
+/* The statements: challenges, boundary pushes and instance numbering of mh_check_balance_*_traces.  No state of mh_miden /
+ * mh_precompile is touched. */
+int mh_fill_multiplicities_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* const traces[3], const uint64_t* public_values,
+                                        const uint64_t* aux_inputs, size_t n_aux_inputs, const mh_mult_slot* slots, size_t n_slots,
+                                        uint64_t* n_written, mh_balance_entry* entries, size_t entry_cap, size_t* n_entries,
+                                        mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);
+int mh_fill_multiplicities_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_trace* const traces[MH_PRECOMPILE_NUM_AIRS],
+                                             const uint64_t public_root[4], const mh_mult_slot* slots, size_t n_slots, uint64_t* n_written,
+                                             mh_balance_entry* entries, size_t entry_cap, size_t* n_entries, mh_balance_push* pushes,
+                                             size_t push_cap, size_t* n_pushes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ EXPORTS = [
     "mh_miden_challenger_state", "mh_miden_hash_kernel_digests", "mh_miden_pre_observe", "mh_miden_eval_external", "mh_miden_air_blob",
     "mh_check_constraints", "mh_constraint_fold", "mh_check_miden", "mh_check_miden_traces", "mh_check_precompile", "mh_check_precompile_traces",
     "mh_check_balance", "mh_check_balance_miden", "mh_check_balance_miden_traces", "mh_check_balance_precompile", "mh_check_balance_precompile_traces",
+    "mh_fill_multiplicities", "mh_fill_multiplicities_miden_traces", "mh_fill_multiplicities_precompile_traces",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
@@ -189,6 +190,53 @@ def check_balance(ctx, lookups, traces, randomness, boundary=(), preprocessed=No
                                     bs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(len(boundary)), flags, ent, ecap, ne, psh, pcap, np_)
 
     return _run_balance(ctx, call)
+
+
+# ---- multiplicity columns (include/midenhip.h mh_fill_multiplicities*) ----
+class MultSlot(C.Structure):
+    """mh_mult_slot: fraction `fraction` of LogUp column `lookup_column` of instance `instance` has a multiplicity that is affine in
+    main-trace column `main_column`."""
+    _fields_ = [("instance", C.c_int32), ("lookup_column", C.c_uint32), ("fraction", C.c_uint32), ("main_column", C.c_uint32)]
+
+
+def _slot_array(slots):
+    """[(instance, lookup_column, fraction, main_column) | MultSlot] -> (ctypes array, count)"""
+    sl = [s if isinstance(s, MultSlot) else MultSlot(*[int(x) for x in s]) for s in slots]
+    return (MultSlot * max(1, len(sl)))(*sl), C.c_size_t(len(sl))
+
+
+def _run_fill(ctx, call):
+    """call(n_written_ptr, entries, ...) as _run_balance's: a second run (short buffers) finds the traces filled and writes the same."""
+    written = C.c_uint64(0)
+    report = _run_balance(ctx, lambda *out: call(C.byref(written), *out))
+    return written.value, report
+
+
+def fill_multiplicities(ctx, lookups, traces, slots, randomness, boundary=(), preprocessed=None):
+    """mh_fill_multiplicities: fill the multiplicity cells the slots name, in place, in the device storage of `traces` (Trace objects),
+    so that every key's net is zero; then the exact balance check.  slots: [(instance, lookup_column, fraction, main_column)];
+    randomness / boundary / preprocessed as check_balance.  -> (cells written, [BalanceEntry]); [] when every bus balances."""
+    lib = ctx.lib
+    n = len(lookups)
+    if len(traces) != n or (preprocessed is not None and len(preprocessed) != n):
+        raise MidenHipError("fill_multiplicities: one trace (and one preprocessed matrix or None) per lookup program expected")
+    if not all(isinstance(t, Trace) for t in traces):
+        raise MidenHipError("fill_multiplicities: Trace objects expected (the traces are filled in place on the device)")
+    pr = [_as_trace(ctx, t) for t in (preprocessed if preprocessed is not None else [None] * n)]
+    la = (C.c_void_p * max(1, n))(*[l.h for l in lookups])
+    ta = (C.c_void_p * max(1, n))(*[t.h for t in traces])
+    pa = (C.c_void_p * max(1, n))(*[t.h if t is not None else None for t in pr])
+    rnd = _arr([int(x) for r in randomness for x in r] or [0])
+    bd = _arr([int(x) for d, _ in boundary for x in d] or [0])
+    bs = np.ascontiguousarray([int(s) for _, s in boundary] or [0], dtype=np.int32)
+    sa, ns = _slot_array(slots)
+
+    def call(written, ent, ecap, ne, psh, pcap, np_):
+        return lib.mh_fill_multiplicities(ctx.h, C.c_int(n), la, ta, pa, _ptr(rnd), C.c_size_t(len(randomness)), _ptr(bd),
+                                          bs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(len(boundary)), sa, ns, written, ent, ecap, ne,
+                                          psh, pcap, np_)
+
+    return _run_fill(ctx, call)
 
 
 def load_library():
@@ -1427,6 +1475,20 @@ class Miden:
                                                            flags, *out)
         return _run_balance(self.ctx, call)
 
+    def fill_multiplicities(self, traces, public_values, aux_inputs, slots):
+        """mh_fill_multiplicities_miden_traces: fill the multiplicity cells `slots` name ([(instance, lookup_column, fraction,
+        main_column)], instance 0 / 1 / 2 = core / chiplets / poseidon2) in the three Trace objects, in place, under check()'s challenges
+        and boundary pushes -> (cells written, [BalanceEntry])."""
+        lib = self.ctx.lib
+        if len(traces) != 3 or not all(isinstance(t, Trace) for t in traces):
+            raise MidenHipError("Miden.fill_multiplicities: three Trace objects expected")
+        pv, aux = _arr([int(x) for x in public_values]), _arr([int(x) for x in aux_inputs] or [0])
+        tr = (C.c_void_p * 3)(*[t.h for t in traces])
+        sa, ns = _slot_array(slots)
+        call = lambda written, *out: lib.mh_fill_multiplicities_miden_traces(self.ctx.h, self.h, tr, _ptr(pv), _ptr(aux),
+                                                                             C.c_size_t(len(aux_inputs)), sa, ns, written, *out)
+        return _run_fill(self.ctx, call)
+
     def free(self):
         if getattr(self, "h", None) and self.ctx.h:
             self.ctx.lib.mh_miden_free(self.h)
@@ -1555,6 +1617,19 @@ class Precompile:
             lh = (C.c_int * 12)(*lg)
             call = lambda *out: lib.mh_check_balance_precompile(self.ctx.h, self.h, ptrs, lh, _ptr(root), flags, *out)
         return _run_balance(self.ctx, call)
+
+    def fill_multiplicities(self, traces, public_root, slots):
+        """mh_fill_multiplicities_precompile_traces: fill the multiplicity cells `slots` name ([(instance, lookup_column, fraction,
+        main_column)], instance = chiplet index) in the twelve Trace objects, in place, under check()'s challenges and the verifier's
+        fixed consumes -> (cells written, [BalanceEntry])."""
+        lib = self.ctx.lib
+        if len(traces) != 12 or not all(isinstance(t, Trace) for t in traces):
+            raise MidenHipError("Precompile.fill_multiplicities: twelve Trace objects expected")
+        root = _arr([int(x) for x in public_root])
+        tr = (C.c_void_p * 12)(*[t.h for t in traces])
+        sa, ns = _slot_array(slots)
+        call = lambda written, *out: lib.mh_fill_multiplicities_precompile_traces(self.ctx.h, self.h, tr, _ptr(root), sa, ns, written, *out)
+        return _run_fill(self.ctx, call)
 
     def free(self):
         if getattr(self, "h", None) and self.ctx.h:

@@ -33,6 +33,9 @@ DEC_ADDR, DEC_OP_BITS, DEC_HASHER, DEC_IN_SPAN, DEC_GROUP_COUNT, DEC_OP_INDEX = 
 DEC_BATCH_FLAGS, DEC_EXTRA = [25, 26, 27], [28, 29]
 STACK_TOP, STACK_B0, STACK_B1, STACK_H0 = list(range(30, 46)), 46, 47, 48
 RANGE_M, RANGE_V = 49, 50
+# mh_fill_multiplicities: the range checker's multiplicity column (RangeChecker::emit_table_rows' counts) as (lookup_column, fraction,
+# main_column) of the core lookup program; instance 0 of the Miden statement
+RANGE_M_MULT_SLOTS = [(0, 14, RANGE_M)]
 
 # ---- opcodes (core/src/operations/mod.rs:29-129) ----------------------------------------------------------------------------------
 OPC = dict(

@@ -15,74 +15,13 @@
 //           denominator on the host, and a second pass over the pushes finds each live push's slot and keeps those of reported entries.
 // push id = instance base + row * K + fraction; lane order inside an instance is fraction-major (consecutive lanes = consecutive rows of
 // one plane: coalesced).
-#include "../../include/midenhip.h"
-#include "air.hpp"
-#include "gl.cuh"
-#include "kernels.hpp"
+#include "balance.cuh"
 #include <algorithm>
 #include <memory>
 #include <string>
 
 static constexpr size_t BAL_MAX_COLLECT = (size_t)1 << 22;  // pushes collected for a report (include/midenhip.h)
-static constexpr int BT = 256, BI = 4, BTILE = BT * BI;
-
-struct BalInst {
-  const u64* planes;  // [2 * n_out][n]
-  u64 n;              // rows = plane stride
-  u64 base;           // first push id (= first lane) of the instance
-  u32 K;              // fractions per row
-  u32 ext_off;        // offset of its output kinds in BalArgs::ext
-  int log_n;          // lane -> (fraction, row) split; 63 for the boundary instance (K = 1, any n)
-};
-struct BalArgs {
-  const BalInst* inst;
-  u32 n_inst;
-  const unsigned char* ext;  // per instance [2K]: is output (m_0, d_0, m_1, ...) EF-valued?
-  u64 total;                 // pushes of all instances, live or not
-};
-struct BalTable {
-  unsigned long long* claim;  // [S] push id + 1 of the claimant, 0 = empty
-  unsigned long long* lo[2];  // [S] per coordinate: sum of the multiplicities mod 2^64 (after k_bal_final: the net, canonical)
-  unsigned long long* hi[2];  // [S] carries out of lo
-  unsigned long long* cnt;    // [S] live pushes
-  u64 mask;                   // S - 1
-};
-
-__device__ __forceinline__ u32 bal_instance(const BalArgs& a, u64 id) {
-  u32 i = 0;
-  while (i + 1 < a.n_inst && id >= a.inst[i + 1].base) i++;
-  return i;
-}
-// canonical value of output `out` of an instance on row r
-__device__ __forceinline__ e2 bal_value(const BalArgs& a, const BalInst& in, u32 out, u64 r) {
-  const u64* p = in.planes + (size_t)(2 * out) * in.n + r;
-  return e2{gl_canon(p[0]), a.ext[in.ext_off + out] ? gl_canon(p[in.n]) : 0};
-}
-struct BalLane {
-  const BalInst* in;
-  u64 row, id;
-  u32 k;
-};
-__device__ __forceinline__ BalLane bal_lane(const BalArgs& a, u64 t) {
-  const BalInst& in = a.inst[bal_instance(a, t)];
-  const u64 l = t - in.base;
-  const u32 k = (u32)(l >> in.log_n);
-  const u64 r = l & (((u64)1 << in.log_n) - 1);
-  return BalLane{&in, r, in.base + r * in.K + k, k};
-}
-__device__ __forceinline__ e2 bal_denominator(const BalArgs& a, u64 id) {
-  const BalInst& in = a.inst[bal_instance(a, id)];
-  const u64 l = id - in.base;
-  return bal_value(a, in, 2 * (u32)(l % in.K) + 1, l / in.K);
-}
-// the keys hold the challenges: uniform already; one multiply-xorshift round spreads both words over the low bits
-__device__ __forceinline__ u64 bal_hash(e2 d) {
-  u64 x = d.c0 ^ (d.c1 * 0x9E3779B97F4A7C15ULL);
-  x ^= x >> 32;
-  x *= 0xD6E8FEB86659FD93ULL;
-  x ^= x >> 32;
-  return x;
-}
+static constexpr int BI = 4, BTILE = BT * BI;
 
 // ---- pass 1: live count per tile, zero denominators, (SCREEN) sum of m / d per tile ----
 template <bool SCREEN>
@@ -173,22 +112,6 @@ __global__ __launch_bounds__(BT) void k_bal_totals(const u64* __restrict__ tile_
 }
 
 // ---- pass 2: net every live push into its key's slot ----
-// INSERT: claim an empty slot on the way.  Otherwise (the table is complete) -> the slot of a key that is present.
-template <bool INSERT>
-__device__ __forceinline__ u64 bal_probe(const BalArgs& a, const BalTable& tb, e2 d, u64 id) {
-  u64 slot = bal_hash(d) & tb.mask;
-  for (;;) {  // ends: the load factor is <= 1/2, so an empty slot exists (INSERT); the key was inserted (lookup)
-    unsigned long long cur = __hip_atomic_load(&tb.claim[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (INSERT && cur == 0) {
-      cur = atomicCAS(&tb.claim[slot], 0ULL, (unsigned long long)(id + 1));
-      if (cur == 0) return slot;
-    }
-    if (cur == id + 1) return slot;
-    if (cur != 0 && e2_eq(bal_denominator(a, cur - 1), d)) return slot;
-    if (!INSERT && cur == 0) return slot;  // unreachable for a complete table; never spin
-    slot = (slot + 1) & tb.mask;
-  }
-}
 __global__ __launch_bounds__(BT) void k_bal_insert(BalArgs a, BalTable tb) {
   const u64 t = (u64)blockIdx.x * BT + threadIdx.x;
   if (t >= a.total) return;
@@ -197,13 +120,7 @@ __global__ __launch_bounds__(BT) void k_bal_insert(BalArgs a, BalTable tb) {
   if (e2_is_zero(m)) return;
   const e2 d = bal_value(a, *ln.in, 2 * ln.k + 1, ln.row);
   const u64 slot = bal_probe<true>(a, tb, d, ln.id);
-  const u64 mc[2] = {m.c0, m.c1};
-#pragma unroll
-  for (int j = 0; j < 2; j++) {
-    if (!mc[j]) continue;
-    const unsigned long long old = atomicAdd(&tb.lo[j][slot], (unsigned long long)mc[j]);
-    if (old + mc[j] < old) atomicAdd(&tb.hi[j][slot], 1ULL);  // the low word wrapped: exactly one of the adders of a wrap sees it
-  }
+  bal_accumulate(tb, slot, m);
   atomicAdd(&tb.cnt[slot], 1ULL);
 }
 // per slot: (hi, lo) -> the net multiplicity mod p (into lo); flag = it is not zero
@@ -211,12 +128,7 @@ __global__ __launch_bounds__(BT) void k_bal_final(BalTable tb, u32* __restrict__
   const u64 s = (u64)blockIdx.x * BT + threadIdx.x;
   if (s > tb.mask) return;
   u32 f = 0;
-  if (tb.claim[s]) {
-    const u64 n0 = gl_reduce128(tb.hi[0][s], tb.lo[0][s]), n1 = gl_reduce128(tb.hi[1][s], tb.lo[1][s]);
-    tb.lo[0][s] = n0;
-    tb.lo[1][s] = n1;
-    f = (n0 | n1) != 0;
-  }
+  if (tb.claim[s]) f = bal_reduce_slot(tb, s);
   flags[s] = f;
 }
 // the reported slots -> {denom c0, c1, net c0, c1, pushes, slot}
@@ -255,21 +167,21 @@ __global__ __launch_bounds__(BT) void k_bal_pushes(BalArgs a, const u32* __restr
   o[0] = ln.id; o[1] = mark[t] - 1; o[2] = mm.c0; o[3] = mm.c1;
 }
 
-namespace {
-struct BalanceInput {
-  const mh_lookup* lk;
-  const mh_trace* main;
-  const mh_trace* prep;
-};
-struct BalanceReport {
-  std::vector<mh_balance_entry> entries;
-  std::vector<mh_balance_push> pushes;
-  size_t n_pushes = 0;  // exact, also when `pushes` was not collected
-};
-inline unsigned grid_for(u64 n) { return (unsigned)((n + BT - 1) / BT); }
+void balance_boundary_planes(mh_ctx* c, const std::vector<BoundaryPush>& boundary, DevBuf& planes) {
+  const size_t nb = boundary.size();
+  std::vector<u64> h(4 * nb, 0);
+  for (size_t i = 0; i < nb; i++) {
+    h[i] = boundary[i].sign > 0 ? 1 : GL_P - 1;
+    h[2 * nb + i] = boundary[i].denom.c0;
+    h[3 * nb + i] = boundary[i].denom.c1;
+  }
+  planes.alloc(h.size() * 8);
+  HIP_CHECK(hipMemcpyAsync(planes.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_CHECK(hipStreamSynchronize(c->stream));  // `h` is pageable and leaves scope
+}
 
 void balance_run(mh_ctx* c, const std::vector<BalanceInput>& in, const std::vector<e2>& rnd, const std::vector<BoundaryPush>& boundary,
-                 bool exact, BalanceReport& rep) {
+                 bool exact, BalanceReport& rep, std::vector<DevBuf>* have) {
   const size_t n_in = in.size();
   // the planes of every instance stay alive together: the table compares keys by re-reading them
   std::vector<DevBuf> planes(n_in);
@@ -281,7 +193,8 @@ void balance_run(mh_ctx* c, const std::vector<BalanceInput>& in, const std::vect
     ProfScope ps(c, "balance_planes");
     for (size_t i = 0; i < n_in; i++) {
       const mh_lookup* lk = in[i].lk;
-      lookup_planes(c, lk, in[i].main, in[i].prep, rnd, planes[i]);
+      if (have && (*have)[i].p) planes[i] = std::move((*have)[i]);
+      else lookup_planes(c, lk, in[i].main, in[i].prep, rnd, planes[i]);
       const u64 n = (u64)1 << in[i].main->log_n;
       inst.push_back(BalInst{planes[i].u(), n, total, (u32)lk->n_fractions(), (u32)ext.size(), in[i].main->log_n});
       ext.insert(ext.end(), lk->out_ext.begin(), lk->out_ext.begin() + 2 * lk->n_fractions());
@@ -290,15 +203,7 @@ void balance_run(mh_ctx* c, const std::vector<BalanceInput>& in, const std::vect
   }
   const size_t nb = boundary.size();
   if (nb) {  // one more instance: K = 1, m = +-1 (base field), d = the denominator
-    std::vector<u64> h(4 * nb, 0);
-    for (size_t i = 0; i < nb; i++) {
-      h[i] = boundary[i].sign > 0 ? 1 : GL_P - 1;
-      h[2 * nb + i] = boundary[i].denom.c0;
-      h[3 * nb + i] = boundary[i].denom.c1;
-    }
-    bplanes.alloc(h.size() * 8);
-    HIP_CHECK(hipMemcpyAsync(bplanes.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));  // `h` is pageable and leaves scope
+    balance_boundary_planes(c, boundary, bplanes);
     inst.push_back(BalInst{bplanes.u(), (u64)nb, total, 1, (u32)ext.size(), 63});
     ext.push_back(0);
     ext.push_back(1);
@@ -460,7 +365,6 @@ void balance_validate(mh_ctx* c, const std::vector<BalanceInput>& in) {
     MH_REQUIRE(b.main->width == b.lk->main_width, "trace width does not match the lookup program");
   }
 }
-}  // namespace
 
 int balance_statement(mh_ctx* c, int n_airs, mh_air* const* airs, mh_trace* const* traces, const mh_trace* const* preps,
                       const u64 challenger_state[12], const u64* pre_observe, size_t n_pre,

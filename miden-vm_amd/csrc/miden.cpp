@@ -444,10 +444,12 @@ int mh_check_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* const traces
   return check_common(ctx, m, traces, public_values, aux_inputs, n_aux_inputs, flags, out, cap, n_entries);
 }
 
-// the bus balance of this statement (balance.hip) with check_common's challenges and eval_external's boundary pushes
+// the bus balance of this statement (balance.hip) with check_common's challenges and eval_external's boundary pushes; n_written != null:
+// mh_fill_multiplicities over the same statement (multiplicity.hip; `flags` unused)
 static int balance_common(mh_ctx* ctx, const mh_miden* m, mh_trace* const* traces, const uint64_t* public_values, const uint64_t* aux_inputs,
                           size_t n_aux_inputs, int flags, mh_balance_entry* entries, size_t entry_cap, size_t* n_entries, mh_balance_push* pushes,
-                          size_t push_cap, size_t* n_pushes) {
+                          size_t push_cap, size_t* n_pushes, const mh_mult_slot* slots = nullptr, size_t n_slots = 0,
+                          uint64_t* n_written = nullptr) {
   if (!ctx || !m || m->ctx != ctx || !n_entries || !n_pushes) return MH_ERR_INVALID;
   mh_pcs_params prm;
   mh_miden_pcs_params(&prm);
@@ -461,6 +463,9 @@ static int balance_common(mh_ctx* ctx, const mh_miden* m, mh_trace* const* trace
   auto boundary = [&](const std::vector<e2>& rnd, std::vector<BoundaryPush>& out) {
     return rnd.size() >= 2 && boundary_pushes(Challenges(rnd[0], rnd[1]), aux_inputs, n_aux_inputs, out);
   };
+  if (n_written)
+    return fill_statement(ctx, 3, m->airs, traces, nullptr, state, pre, MH_MIDEN_PRE_OBSERVE_FELTS, boundary, names, slots, n_slots, n_written,
+                          entries, entry_cap, n_entries, pushes, push_cap, n_pushes);
   return balance_statement(ctx, 3, m->airs, traces, nullptr, state, pre, MH_MIDEN_PRE_OBSERVE_FELTS, boundary, names, flags, entries, entry_cap,
                            n_entries, pushes, push_cap, n_pushes);
 }
@@ -492,6 +497,14 @@ int mh_check_balance_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* cons
                                   size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes) {
   if (!traces) return MH_ERR_INVALID;
   return balance_common(ctx, m, traces, public_values, aux_inputs, n_aux_inputs, flags, entries, entry_cap, n_entries, pushes, push_cap, n_pushes);
+}
+int mh_fill_multiplicities_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* const traces[3], const uint64_t* public_values,
+                                        const uint64_t* aux_inputs, size_t n_aux_inputs, const mh_mult_slot* slots, size_t n_slots,
+                                        uint64_t* n_written, mh_balance_entry* entries, size_t entry_cap, size_t* n_entries,
+                                        mh_balance_push* pushes, size_t push_cap, size_t* n_pushes) {
+  if (!traces || !n_written) return MH_ERR_INVALID;
+  return balance_common(ctx, m, traces, public_values, aux_inputs, n_aux_inputs, 0, entries, entry_cap, n_entries, pushes, push_cap, n_pushes,
+                        slots, n_slots, n_written);
 }
 
 }  // extern "C"

@@ -343,9 +343,11 @@ int mh_check_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_trace* const tr
   return check_common(ctx, s, traces, public_root, flags, out, cap, n_entries);
 }
 
-// the bus balance of the session (balance.hip; bus_balance.rs:25-108) with check_common's challenges and the verifier's fixed consumes
+// the bus balance of the session (balance.hip; bus_balance.rs:25-108) with check_common's challenges and the verifier's fixed consumes;
+// n_written != null: mh_fill_multiplicities over the same statement (multiplicity.hip; `flags` unused)
 static int balance_common(mh_ctx* ctx, mh_precompile* s, mh_trace* const* traces, const uint64_t* public_root, int flags, mh_balance_entry* entries,
-                          size_t entry_cap, size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes) {
+                          size_t entry_cap, size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes,
+                          const mh_mult_slot* slots = nullptr, size_t n_slots = 0, uint64_t* n_written = nullptr) {
   if (!ctx || !s || s->ctx != ctx || !public_root || !n_entries || !n_pushes) return MH_ERR_INVALID;
   mh_pcs_params prm;
   mh_precompile_pcs_params(&prm);
@@ -360,6 +362,9 @@ static int balance_common(mh_ctx* ctx, mh_precompile* s, mh_trace* const* traces
   auto boundary = [](const std::vector<e2>& rnd, std::vector<BoundaryPush>& out) {
     return rnd.size() >= 2 && precompile_session_boundary(true, rnd[0], rnd[1], out);
   };
+  if (n_written)
+    return fill_statement(ctx, N_AIRS, s->airs, traces, preps, state, pre, MH_PRECOMPILE_PRE_OBSERVE_FELTS, boundary, names, slots, n_slots,
+                          n_written, entries, entry_cap, n_entries, pushes, push_cap, n_pushes);
   return balance_statement(ctx, N_AIRS, s->airs, traces, preps, state, pre, MH_PRECOMPILE_PRE_OBSERVE_FELTS, boundary, names, flags, entries,
                            entry_cap, n_entries, pushes, push_cap, n_pushes);
 }
@@ -388,6 +393,13 @@ int mh_check_balance_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_trace* 
                                        size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes) {
   if (!traces) return MH_ERR_INVALID;
   return balance_common(ctx, s, traces, public_root, flags, entries, entry_cap, n_entries, pushes, push_cap, n_pushes);
+}
+int mh_fill_multiplicities_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_trace* const traces[MH_PRECOMPILE_NUM_AIRS],
+                                             const uint64_t public_root[4], const mh_mult_slot* slots, size_t n_slots, uint64_t* n_written,
+                                             mh_balance_entry* entries, size_t entry_cap, size_t* n_entries, mh_balance_push* pushes,
+                                             size_t push_cap, size_t* n_pushes) {
+  if (!traces || !n_written) return MH_ERR_INVALID;
+  return balance_common(ctx, s, traces, public_root, 0, entries, entry_cap, n_entries, pushes, push_cap, n_pushes, slots, n_slots, n_written);
 }
 
 }  // extern "C"

@@ -306,6 +306,38 @@ class Lookup:
         self.num_aux_cols = self.num_cols + self.num_regs               # the aux trace it builds: LogUp columns, then registers
         self.blob = builder.blob()
 
+    def multiplicity_slots(self, columns):
+        """The slot list of mh_fill_multiplicities for an AIR author who names the multiplicity columns: [(lookup_column, fraction,
+        main_column)] for every fraction whose MULTIPLICITY expression reads one of the main-trace `columns` at row offset 0, in program
+        order.  Structural only (it does not check that the dependence is affine, nor that the denominators stay clear of the columns):
+        the library's numeric probing is the authority."""
+        w = [int(x) for x in self.blob]
+        k = 12
+        for _ in range(w[6]):
+            k += 1 + w[k]
+        nodes = []
+        for _ in range(w[8]):
+            nodes.append((w[k] & 0xFF, (w[k] >> 8) & ((1 << 28) - 1), w[k] >> 36))
+            k += 2
+        reads = []  # per node the wanted columns below it (children precede their parents)
+        wanted = {int(c) for c in columns}
+        for op, a, b in nodes:
+            if op == OP_MAIN:
+                reads.append(frozenset([a]) if b == 0 and a in wanted else frozenset())
+            elif op in (OP_ADD, OP_SUB, OP_MUL):
+                reads.append(reads[a] | reads[b])
+            elif op == OP_NEG:
+                reads.append(reads[a])
+            else:
+                reads.append(frozenset())
+        out = []
+        for col in range(w[2]):
+            cnt = w[k]
+            for j in range(cnt):
+                out.extend((col, j, c) for c in sorted(reads[w[k + 1 + 2 * j]]))
+            k += 1 + 2 * cnt
+        return out
+
 
 # ---- the LogUp aux builder of an AIR, derived from its constraint DAG ---------------------------------------------------------
 def parse_air_blob(blob):

@@ -158,6 +158,11 @@ def byte_pair_lut_air(host_aux=None):
     return dag.Air(b, _host_aux(lookup, host_aux, prep), "byte_pair_lut", preprocessed=prep), lookup
 
 
+# mh_fill_multiplicities: the table's three multiplicity columns (the per-pair ledger of byte_pair_lut.rs:134-226, filled from the
+# consumers' pushes on the device) as (lookup_column, fraction, main_column); the instance is the chiplet's index in the session
+BYTE_PAIR_LUT_MULT_SLOTS = [(0, 0, 0), (1, 0, 1), (1, 1, 2)]
+
+
 # ---- EcGroups ------------------------------------------------------------------------------------------------------------------------
 EC_GROUPS_COLS = 6  # ptr, a_ptr, b_ptr, bound_ptr, scalar_bound_ptr, mult (ec/groups.rs:59-74)
 
