@@ -129,6 +129,14 @@ def set_lmcs(name):
     lib().orc_set_lmcs(C.c_int({"poseidon2": 0, "blake3": 1, "keccak": 2, "rpo": 3, "rpx": 4}[name]))
 
 
+def lmcs_compress(l, r):
+    """One Merkle node under the hasher set_lmcs chose (orc_lmcs_compress): four u64 words in, four out."""
+    l, r = arr(l), arr(r)
+    out = np.zeros(4, dtype=np.uint64)
+    lib().orc_lmcs_compress(ptr(l), ptr(r), ptr(out))
+    return out
+
+
 def blake3(data):
     data = bytes(data)
     out = C.create_string_buffer(32)
