@@ -44,6 +44,17 @@ pub struct mh_mult_slot {
     pub main_column: u32,
 }
 
+/// mh_poseidon2_trace_build / mh_miden_poseidon2_trace: what was built, or the defect that refused the input (see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_p2_trace_info {
+    pub n_requests: u64,
+    pub n_input_rows: u64,
+    pub log_n: i32,
+    pub defect: i32,
+    pub defect_row: u64,
+}
+
 /// An encoded denominator whose net multiplicity is not zero (mh_check_balance*; the reference's `Unmatched`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -419,4 +430,7 @@ unsafe extern "C" {
     pub fn mh_fill_multiplicities(ctx: *mut mh_ctx, n: c_int, lookups: *const *const mh_lookup, traces: *const *mut mh_trace, preprocessed: *const *const mh_trace, randomness: *const u64, n_randomness: usize, boundary_denoms: *const u64, boundary_signs: *const i32, n_boundary: usize, slots: *const mh_mult_slot, n_slots: usize, n_written: *mut u64, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
     pub fn mh_fill_multiplicities_miden_traces(ctx: *mut mh_ctx, m: *const mh_miden, traces: *const *mut mh_trace, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, slots: *const mh_mult_slot, n_slots: usize, n_written: *mut u64, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
     pub fn mh_fill_multiplicities_precompile_traces(ctx: *mut mh_ctx, s: *mut mh_precompile, traces: *const *mut mh_trace, public_root: *const u64, slots: *const mh_mult_slot, n_slots: usize, n_written: *mut u64, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
+    // the Poseidon2 permutation trace of the Miden statement, built on the device (csrc/p2_trace.hip); info may be null
+    pub fn mh_poseidon2_trace_build(ctx: *mut mh_ctx, states: *const u64, multiplicities: *const u64, k: usize, log_n: c_int, out: *mut *mut mh_trace, info: *mut mh_p2_trace_info) -> c_int;
+    pub fn mh_miden_poseidon2_trace(ctx: *mut mh_ctx, chiplets: *const mh_trace, log_n: c_int, out: *mut *mut mh_trace, info: *mut mh_p2_trace_info) -> c_int;
 }

@@ -957,6 +957,47 @@ int mh_fill_multiplicities_precompile_traces(mh_ctx* ctx, mh_precompile* s, mh_t
                                              mh_balance_entry* entries, size_t entry_cap, size_t* n_entries, mh_balance_push* pushes,
                                              size_t push_cap, size_t* n_pushes);
 
+/* ---- the Poseidon2 permutation trace of the Miden statement, built on the device -------------------------------------------------------
+ * The third main trace of the statement (16 columns: witnesses[3] | state[12] | perm_id) holds no information of its own:
+ * fill_poseidon2_permutation_trace (processor/src/trace/chiplets/hasher/trace.rs:361-408) derives it from a list of (input state,
+ * multiplicity) requests, one 16-row cycle each, then zero-state zero-multiplicity padding cycles with consecutive ids; and the list is
+ * what record_perm_request (hasher/mod.rs:469-480) collects from the hasher controller's input rows of the chiplets trace.  Device
+ * stage: csrc/p2_trace.hip.  Every cell written is canonical.  The result is an ordinary mh_trace of this context: traces[2] of
+ * mh_prove_miden_traces, mh_check_miden_traces, mh_check_balance_miden_traces and mh_fill_multiplicities_miden_traces.
+ *   from a list      cycle c < k: states[c], multiplicities[c], both reduced mod p.
+ *   from chiplets    a controller input row has column 0 = 0 (the hasher's chiplet selector) and column 1 = 1 (controller s0); memory
+ *                    rows (1, 1, ..) and controller padding rows (0, 0, 1, 0) are not.  Its request id is column 20 (perm_id), its state
+ *                    columns 4..15.  k = the largest id + 1; cycle c's state is that of the LOWEST input row with id c, its multiplicity
+ *                    the number of input rows with id c.
+ * (k + 1) * 16 <= 2^log_n is required (one padding cycle at least, as in the reference); log_n lies in 6..32, or is -1:
+ * max(6, ceil log2((k + 1) * 16)).  k == 0 gives all padding.
+ * A null pointer, a chiplets trace that is not 22 wide or belongs to another context and a log_n out of range are refused before any
+ * launch.  A DEFECT of the input is found on the device: *out = NULL, MH_ERR_INVALID, `info` filled, mh_last_error names kind and row.
+ * Kinds, reported in this order, always the lowest row / id of the kind:
+ *   1  the perm_id of an input row lies beyond the id table (N/2 + 1 entries for N chiplets rows); defect_row = the row.  n_requests
+ *      is then a partial value: the largest id + 1 over the input rows whose id lies inside the table
+ *   3  an input row carries another state than the lowest input row of its id; defect_row = the row
+ *   2  an id below k that no input row requests; defect_row = the id
+ *   4  (k + 1) * 16 > 2^log_n; defect_row = the lowest id without a cycle of its own, 2^log_n / 16 - 1
+ * The context stays usable.  The call orders itself after a pending mh_trace_upload_async / _cols_async of the chiplets trace, waits
+ * once for five words of the scan and returns with the trace's kernel enqueued: any later call on the context may use *out at once.
+ * Two calls on the same input leave the same bytes.
+ * Not in scope: the precompile prover's Poseidon2Air (another AIR, with cube registers), sharded contexts, and deriving the chiplets
+ * trace itself. */
+typedef struct mh_p2_trace_info {
+  uint64_t n_requests;     /* k: distinct permutation requests = cycles that carry one */
+  uint64_t n_input_rows;   /* controller input rows read (0 for the host-list entry) */
+  int32_t  log_n;          /* height of the trace built */
+  int32_t  defect;         /* 0 none, 1 id out of range, 2 id gap, 3 conflicting states for one id, 4 too many requests for log_n */
+  uint64_t defect_row;     /* lowest chiplets row (kinds 1, 3) or lowest id (kinds 2, 4) */
+} mh_p2_trace_info;
+/* fill_poseidon2_permutation_trace from a host request list: states [k][12], multiplicities [k] (any uint64_t, reduced mod p) */
+int mh_poseidon2_trace_build(mh_ctx* ctx, const uint64_t* states, const uint64_t* multiplicities, size_t k,
+                             int log_n /* -1: max(6, ceil log2((k + 1) * 16)) */, mh_trace** out, mh_p2_trace_info* info /* may be NULL */);
+/* the same, the requests read from a device-resident chiplets trace (width 22) */
+int mh_miden_poseidon2_trace(mh_ctx* ctx, const mh_trace* chiplets, int log_n /* -1 as above */, mh_trace** out,
+                             mh_p2_trace_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

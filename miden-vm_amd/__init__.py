@@ -40,6 +40,7 @@ EXPORTS = [
     "mh_check_constraints", "mh_constraint_fold", "mh_check_miden", "mh_check_miden_traces", "mh_check_precompile", "mh_check_precompile_traces",
     "mh_check_balance", "mh_check_balance_miden", "mh_check_balance_miden_traces", "mh_check_balance_precompile", "mh_check_balance_precompile_traces",
     "mh_fill_multiplicities", "mh_fill_multiplicities_miden_traces", "mh_fill_multiplicities_precompile_traces",
+    "mh_poseidon2_trace_build", "mh_miden_poseidon2_trace",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
@@ -237,6 +238,34 @@ def fill_multiplicities(ctx, lookups, traces, slots, randomness, boundary=(), pr
                                           psh, pcap, np_)
 
     return _run_fill(ctx, call)
+
+
+class P2TraceInfo(C.Structure):
+    """mh_p2_trace_info: k = n_requests cycles carry a request, read from n_input_rows controller input rows (0: a host list); `defect`
+    0 none, 1 id out of range, 2 id gap, 3 conflicting states for one id, 4 too many requests for log_n; `defect_row` the lowest
+    chiplets row (1, 3) or id (2, 4)."""
+    _fields_ = [("n_requests", C.c_uint64), ("n_input_rows", C.c_uint64), ("log_n", C.c_int32), ("defect", C.c_int32), ("defect_row", C.c_uint64)]
+
+    def __repr__(self):
+        return (f"P2TraceInfo(n_requests={self.n_requests}, n_input_rows={self.n_input_rows}, log_n={self.log_n}, defect={self.defect}, "
+                f"defect_row={self.defect_row})")
+
+
+def poseidon2_trace(ctx, states, multiplicities, log_n=None):
+    """mh_poseidon2_trace_build: fill_poseidon2_permutation_trace on the device from a request list -- states [k, 12], multiplicities [k]
+    (any uint64, reduced mod p) -> Trace [2^log_n, 16]; log_n None: max(6, ceil log2((k + 1) * 16)).  `Trace.p2_info` is the call's
+    P2TraceInfo."""
+    st = _arr(states).reshape(-1, 12)
+    mu = _arr(multiplicities).reshape(-1)
+    if mu.size != st.shape[0]:
+        raise MidenHipError("poseidon2_trace: one multiplicity per state")
+    lib = ctx.lib
+    lib.mh_poseidon2_trace_build.argtypes = [C.c_void_p, u64p, u64p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.POINTER(P2TraceInfo)]
+    h, info = C.c_void_p(), P2TraceInfo()
+    ctx.check(lib.mh_poseidon2_trace_build(ctx.h, _ptr(st), _ptr(mu), st.shape[0], -1 if log_n is None else int(log_n), C.byref(h), C.byref(info)))
+    t = Trace.from_handle(ctx, h, int(info.log_n), 16)
+    t.p2_info = info
+    return t
 
 
 def load_library():
@@ -1488,6 +1517,23 @@ class Miden:
         call = lambda written, *out: lib.mh_fill_multiplicities_miden_traces(self.ctx.h, self.h, tr, _ptr(pv), _ptr(aux),
                                                                              C.c_size_t(len(aux_inputs)), sa, ns, written, *out)
         return _run_fill(self.ctx, call)
+
+    def poseidon2_trace(self, chiplets, log_n=None):
+        """mh_miden_poseidon2_trace: the statement's third main trace derived on the device from the hasher controller's input rows of
+        the device-resident chiplets Trace -> (Trace [2^log_n, 16], P2TraceInfo); log_n None: the smallest height.  A defect of the
+        chiplets trace (a skipped perm_id, two states under one id, an id out of range, a log_n too small) raises MidenHipError with the
+        library's message; `e.info` is the P2TraceInfo naming kind and row."""
+        lib = self.ctx.lib
+        if not isinstance(chiplets, Trace):
+            raise MidenHipError("Miden.poseidon2_trace: a Trace object expected")
+        lib.mh_miden_poseidon2_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(P2TraceInfo)]
+        h, info = C.c_void_p(), P2TraceInfo()
+        rc = lib.mh_miden_poseidon2_trace(self.ctx.h, chiplets.h, -1 if log_n is None else int(log_n), C.byref(h), C.byref(info))
+        if rc != 0:
+            e = MidenHipError(f"libmidenhip error {rc}: {lib.mh_last_error(self.ctx.h).decode()}")
+            e.info = info
+            raise e
+        return Trace.from_handle(self.ctx, h, int(info.log_n), 16), info
 
     def free(self):
         if getattr(self, "h", None) and self.ctx.h:
