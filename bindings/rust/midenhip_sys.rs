@@ -44,6 +44,27 @@ pub struct mh_mult_slot {
     pub main_column: u32,
 }
 
+/// mh_fill_range_table: fraction `fraction` of LogUp column `lookup_column` of instance `instance` is the range table's provider; its
+/// denominator encodes main-trace column `value_column`, its multiplicity is affine in `mult_column`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_range_slot {
+    pub instance: i32,
+    pub lookup_column: u32,
+    pub fraction: u32,
+    pub value_column: u32,
+    pub mult_column: u32,
+}
+
+/// mh_fill_range_table*: the table's size against the declaring trace's height (filled also when the table does not fit).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_range_table_info {
+    pub n_values: u64,
+    pub rows_needed: u64,
+    pub rows_available: u64,
+}
+
 /// mh_poseidon2_trace_build / mh_miden_poseidon2_trace: what was built, or the defect that refused the input (see midenhip.h).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -433,4 +454,7 @@ unsafe extern "C" {
     // the Poseidon2 permutation trace of the Miden statement, built on the device (csrc/p2_trace.hip); info may be null
     pub fn mh_poseidon2_trace_build(ctx: *mut mh_ctx, states: *const u64, multiplicities: *const u64, k: usize, log_n: c_int, out: *mut *mut mh_trace, info: *mut mh_p2_trace_info) -> c_int;
     pub fn mh_miden_poseidon2_trace(ctx: *mut mh_ctx, chiplets: *const mh_trace, log_n: c_int, out: *mut *mut mh_trace, info: *mut mh_p2_trace_info) -> c_int;
+    // the range-check table laid on the device from the statement's lookups, in place (csrc/range_table.hip); info may be null
+    pub fn mh_fill_range_table(ctx: *mut mh_ctx, n: c_int, lookups: *const *const mh_lookup, traces: *const *mut mh_trace, preprocessed: *const *const mh_trace, randomness: *const u64, n_randomness: usize, boundary_denoms: *const u64, boundary_signs: *const i32, n_boundary: usize, slot: *const mh_range_slot, info: *mut mh_range_table_info, n_written: *mut u64, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
+    pub fn mh_fill_range_table_miden_traces(ctx: *mut mh_ctx, m: *const mh_miden, traces: *const *mut mh_trace, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, info: *mut mh_range_table_info, n_written: *mut u64, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
 }

@@ -998,6 +998,53 @@ int mh_poseidon2_trace_build(mh_ctx* ctx, const uint64_t* states, const uint64_t
 int mh_miden_poseidon2_trace(mh_ctx* ctx, const mh_trace* chiplets, int log_n /* -1 as above */, mh_trace** out,
                              mh_p2_trace_info* info /* may be NULL */);
 
+/* ---- the range-check table, laid on the device from the statement's lookups ------------------------------------------------------------
+ * mh_fill_multiplicities counts how often each table row is looked up; this call also lays the table.  From traces whose value column
+ * and multiplicity column hold anything at all it writes both, as RangeChecker::write_range_into_core does (processor/src/trace/range/
+ * mod.rs:82-204): the 16-bit values any push of the statement looks up, 0 and 65535 always, ascending, gaps bridged by rows 3^k apart
+ * (k <= 7, get_num_bridge_rows / write_rows), a trailing (0, 65535) row, the table in the LAST rows_needed rows and zeros above it.
+ * The rule is the reference's and is fixed.  Device stage: csrc/range_table.hip.
+ *   probe    the declaring instance's program on a scratch copy of its trace with the value column 0, then 1.  The slot's denominator
+ *            must be d0 + g * cell with d0, g the same on every row and g != 0, its multiplicity the same in both, and no other
+ *            fraction may differ between the two: otherwise MH_ERR_INVALID, mh_last_error names the first offending fraction.
+ *   mark     every push of the statement with a non-zero multiplicity (boundary pushes included, the slot's own left out) whose
+ *            (d - d0) / g is a base-field value below 2^16 is a lookup of that value.  Pushes of other buses fail this decode because
+ *            the challenges are extension-field values; the verify stage reports whatever would slip through.
+ *   rows     rows_needed = sum over the present values of 1 + get_num_bridge_rows(gap) + 1.  rows_needed > 2^log_n of the declaring
+ *            trace: MH_ERR_INVALID with `info` filled, so the caller can size the trace and call again.
+ *   emit     both columns: zeros in rows [0, n - rows_needed), the table below; multiplicity cells 0.
+ *   fill     mh_fill_multiplicities with the one slot (instance, lookup_column, fraction, mult_column): *n_written, the report, MH_OK /
+ *            MH_ERR_UNSATISFIED are that call's.  The count of value 0 is kept on the table's first row, as the reference does.
+ * A refused call (MH_ERR_INVALID) has written nothing.  A looked-up value of 2^16 or more, or one outside the base field, cannot be
+ * decoded: it gets no row and comes back as an unmatched push in the report (MH_ERR_UNSATISFIED).  Two calls on the same inputs leave
+ * the same bytes.  Lifetime and ordering are those of mh_fill_multiplicities: in place, after a pending mh_trace_upload_async, on the
+ * context's stream, before the trace is committed or proved.
+ * Not in scope: sharded contexts, host matrices, rules other than the 16-bit / 3^k table, deriving the memory rows' own range limbs
+ * (the chiplets trace has to carry them: they are what the memory rows push). */
+typedef struct mh_range_slot {   /* fraction `fraction` of LogUp column `lookup_column` of instance `instance` is the table's provider:
+                                    its denominator encodes main-trace column `value_column`, its multiplicity is affine in `mult_column` */
+  int32_t instance;
+  uint32_t lookup_column, fraction;   /* as in mh_balance_push */
+  uint32_t value_column, mult_column;
+} mh_range_slot;
+typedef struct mh_range_table_info {
+  uint64_t n_values;         /* distinct values in the table (0 and 65535 included) */
+  uint64_t rows_needed;      /* value rows + bridge rows + the trailing row */
+  uint64_t rows_available;   /* height of the declaring instance's trace */
+} mh_range_table_info;
+int mh_fill_range_table(mh_ctx* ctx, int n, const mh_lookup* const* lookups, mh_trace* const* traces,
+                        const mh_trace* const* preprocessed /* or NULL */, const uint64_t* randomness /* EF pairs */, size_t n_randomness,
+                        const uint64_t* boundary_denoms /* EF pairs */, const int32_t* boundary_signs, size_t n_boundary,
+                        const mh_range_slot* slot, mh_range_table_info* info /* may be NULL */, uint64_t* n_written,
+                        mh_balance_entry* entries, size_t entry_cap, size_t* n_entries, mh_balance_push* pushes, size_t push_cap,
+                        size_t* n_pushes);
+/* The Miden statement: the slot is the core trace's range table (instance 0, LogUp column 0 fraction 14, value column 50,
+ * multiplicity column 49); challenges and boundary pushes of mh_check_balance_miden_traces. */
+int mh_fill_range_table_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* const traces[3], const uint64_t* public_values,
+                                     const uint64_t* aux_inputs, size_t n_aux_inputs, mh_range_table_info* info /* may be NULL */,
+                                     uint64_t* n_written, mh_balance_entry* entries, size_t entry_cap, size_t* n_entries,
+                                     mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,7 @@ EXPORTS = [
     "mh_check_constraints", "mh_constraint_fold", "mh_check_miden", "mh_check_miden_traces", "mh_check_precompile", "mh_check_precompile_traces",
     "mh_check_balance", "mh_check_balance_miden", "mh_check_balance_miden_traces", "mh_check_balance_precompile", "mh_check_balance_precompile_traces",
     "mh_fill_multiplicities", "mh_fill_multiplicities_miden_traces", "mh_fill_multiplicities_precompile_traces",
-    "mh_poseidon2_trace_build", "mh_miden_poseidon2_trace",
+    "mh_poseidon2_trace_build", "mh_miden_poseidon2_trace", "mh_fill_range_table", "mh_fill_range_table_miden_traces",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
@@ -238,6 +238,62 @@ def fill_multiplicities(ctx, lookups, traces, slots, randomness, boundary=(), pr
                                           psh, pcap, np_)
 
     return _run_fill(ctx, call)
+
+
+# ---- the range-check table (include/midenhip.h mh_fill_range_table*) ----
+class RangeSlot(C.Structure):
+    """mh_range_slot: fraction `fraction` of LogUp column `lookup_column` of instance `instance` is the range table's provider; its
+    denominator encodes main-trace column `value_column`, its multiplicity is affine in `mult_column`."""
+    _fields_ = [("instance", C.c_int32), ("lookup_column", C.c_uint32), ("fraction", C.c_uint32), ("value_column", C.c_uint32),
+                ("mult_column", C.c_uint32)]
+
+
+class RangeTableInfo(C.Structure):
+    """mh_range_table_info: the table holds n_values distinct values in rows_needed rows (bridge rows and the trailing row included);
+    the declaring trace has rows_available."""
+    _fields_ = [("n_values", C.c_uint64), ("rows_needed", C.c_uint64), ("rows_available", C.c_uint64)]
+
+    def __repr__(self):
+        return f"RangeTableInfo(n_values={self.n_values}, rows_needed={self.rows_needed}, rows_available={self.rows_available})"
+
+
+def _run_range(ctx, call, info):
+    """_run_fill for a call that also fills `info`; a refusal carries it as `e.info`."""
+    try:
+        return _run_fill(ctx, call)[1], info
+    except MidenHipError as e:
+        e.info = info
+        raise
+
+
+def fill_range_table(ctx, lookups, traces, slot, randomness, boundary=(), preprocessed=None):
+    """mh_fill_range_table: lay the range-check table of `slot` = (instance, lookup_column, fraction, value_column, mult_column) from
+    the lookups of the statement, in place, in the device storage of `traces` (Trace objects): the value column and the multiplicity
+    column are overwritten whatever they held.  randomness / boundary / preprocessed as check_balance.
+    -> ([BalanceEntry], RangeTableInfo); [] when every bus balances.  A table that does not fit its trace, or a slot whose denominator
+    is not uniform and affine in the value cell, raises MidenHipError with `e.info`; nothing was written then."""
+    lib = ctx.lib
+    n = len(lookups)
+    if len(traces) != n or (preprocessed is not None and len(preprocessed) != n):
+        raise MidenHipError("fill_range_table: one trace (and one preprocessed matrix or None) per lookup program expected")
+    if not all(isinstance(t, Trace) for t in traces):
+        raise MidenHipError("fill_range_table: Trace objects expected (the traces are filled in place on the device)")
+    pr = [_as_trace(ctx, t) for t in (preprocessed if preprocessed is not None else [None] * n)]
+    la = (C.c_void_p * max(1, n))(*[l.h for l in lookups])
+    ta = (C.c_void_p * max(1, n))(*[t.h for t in traces])
+    pa = (C.c_void_p * max(1, n))(*[t.h if t is not None else None for t in pr])
+    rnd = _arr([int(x) for r in randomness for x in r] or [0])
+    bd = _arr([int(x) for d, _ in boundary for x in d] or [0])
+    bs = np.ascontiguousarray([int(s) for _, s in boundary] or [0], dtype=np.int32)
+    sl = slot if isinstance(slot, RangeSlot) else RangeSlot(*[int(x) for x in slot])
+    info = RangeTableInfo()
+
+    def call(written, ent, ecap, ne, psh, pcap, np_):
+        return lib.mh_fill_range_table(ctx.h, C.c_int(n), la, ta, pa, _ptr(rnd), C.c_size_t(len(randomness)), _ptr(bd),
+                                       bs.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(len(boundary)), C.byref(sl), C.byref(info),
+                                       written, ent, ecap, ne, psh, pcap, np_)
+
+    return _run_range(ctx, call, info)
 
 
 class P2TraceInfo(C.Structure):
@@ -1517,6 +1573,21 @@ class Miden:
         call = lambda written, *out: lib.mh_fill_multiplicities_miden_traces(self.ctx.h, self.h, tr, _ptr(pv), _ptr(aux),
                                                                              C.c_size_t(len(aux_inputs)), sa, ns, written, *out)
         return _run_fill(self.ctx, call)
+
+    def fill_range_table(self, traces, public_values, aux_inputs):
+        """mh_fill_range_table_miden_traces: lay the range-check table (core columns RANGE_V and RANGE_M, core_air.RANGE_TABLE_SLOT) in
+        the core Trace from the lookups of the three Trace objects, in place, under check()'s challenges and boundary pushes; whatever
+        the two columns held is overwritten -> ([BalanceEntry], RangeTableInfo).  A table that does not fit the core trace raises
+        MidenHipError; `e.info` says how many rows it needs."""
+        lib = self.ctx.lib
+        if len(traces) != 3 or not all(isinstance(t, Trace) for t in traces):
+            raise MidenHipError("Miden.fill_range_table: three Trace objects expected")
+        pv, aux = _arr([int(x) for x in public_values]), _arr([int(x) for x in aux_inputs] or [0])
+        tr = (C.c_void_p * 3)(*[t.h for t in traces])
+        info = RangeTableInfo()
+        call = lambda written, *out: lib.mh_fill_range_table_miden_traces(self.ctx.h, self.h, tr, _ptr(pv), _ptr(aux),
+                                                                          C.c_size_t(len(aux_inputs)), C.byref(info), written, *out)
+        return _run_range(self.ctx, call, info)
 
     def poseidon2_trace(self, chiplets, log_n=None):
         """mh_miden_poseidon2_trace: the statement's third main trace derived on the device from the hasher controller's input rows of

@@ -36,6 +36,8 @@ RANGE_M, RANGE_V = 49, 50
 # mh_fill_multiplicities: the range checker's multiplicity column (RangeChecker::emit_table_rows' counts) as (lookup_column, fraction,
 # main_column) of the core lookup program; instance 0 of the Miden statement
 RANGE_M_MULT_SLOTS = [(0, 14, RANGE_M)]
+# mh_fill_range_table: the same fraction as the range table's provider, (lookup_column, fraction, value_column, mult_column)
+RANGE_TABLE_SLOT = (0, 14, RANGE_V, RANGE_M)
 
 # ---- opcodes (core/src/operations/mod.rs:29-129) ----------------------------------------------------------------------------------
 OPC = dict(

@@ -1,5 +1,5 @@
-// What balance.hip (mh_check_balance*) and multiplicity.hip (mh_fill_multiplicities*) share: the lane / push-id arithmetic over the planes
-// of a statement's lookup programs, the open-addressing table in HBM and its probe, and the host stage that nets a statement exactly.
+// What balance.hip (mh_check_balance*), multiplicity.hip (mh_fill_multiplicities*) and range_table.hip (mh_fill_range_table*) share: the
+// lane / push-id arithmetic over the planes of a statement's lookup programs, the open-addressing table in HBM and its probe, and the host stage that nets a statement exactly.
 // See the header comment of balance.hip for the table's protocol.
 #pragma once
 #include "../../include/midenhip.h"
@@ -122,3 +122,13 @@ void balance_run(mh_ctx* c, const std::vector<BalanceInput>& in, const std::vect
 int balance_report(mh_ctx* c, const BalanceReport& rep, const char* const* names, mh_balance_entry* entries, size_t entry_cap,
                    size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);
 void balance_validate(mh_ctx* c, const std::vector<BalanceInput>& in);
+
+// ---- the host side of multiplicity.hip that range_table.hip runs as its last stage ----
+struct FillInput {
+  BalanceInput b;
+  mh_trace* main;  // the same trace, writable
+  int label;       // the caller's instance number (messages)
+};
+// probe, insert, resolve, verify over the slots (slots[i].instance indexes `in`); names: per label, or null
+void fill_run(mh_ctx* c, const std::vector<FillInput>& in, const std::vector<e2>& rnd, const std::vector<BoundaryPush>& boundary,
+              const std::vector<mh_mult_slot>& slots, const char* const* names, u64* n_written, BalanceReport& rep);

@@ -231,3 +231,10 @@ int fill_statement(mh_ctx* c, int n_airs, mh_air* const* airs, mh_trace* const* 
                    const std::function<bool(const std::vector<e2>&, std::vector<BoundaryPush>&)>& boundary, const char* const* names,
                    const mh_mult_slot* slots, size_t n_slots, uint64_t* n_written, mh_balance_entry* entries, size_t entry_cap, size_t* n_entries,
                    mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);
+// range_table.hip: mh_fill_range_table over one statement, with balance_statement's challenges and boundary pushes; the slot names its
+// AIR by its index in `airs`.  Never throws.
+int range_statement(mh_ctx* c, int n_airs, mh_air* const* airs, mh_trace* const* traces, const mh_trace* const* preps,
+                    const u64 challenger_state[12], const u64* pre_observe, size_t n_pre,
+                    const std::function<bool(const std::vector<e2>&, std::vector<BoundaryPush>&)>& boundary, const char* const* names,
+                    const mh_range_slot* slot, mh_range_table_info* info, uint64_t* n_written, mh_balance_entry* entries, size_t entry_cap,
+                    size_t* n_entries, mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);

@@ -506,5 +506,28 @@ int mh_fill_multiplicities_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace
   return balance_common(ctx, m, traces, public_values, aux_inputs, n_aux_inputs, 0, entries, entry_cap, n_entries, pushes, push_cap, n_pushes,
                         slots, n_slots, n_written);
 }
+// the core trace's range table (range_table.hip): RANGE_V = column 50 and RANGE_M = column 49 behind LogUp column 0 fraction 14
+// (constraints/lookup/buses/block_stack_and_range_logcap.rs), with balance_common's challenges and boundary pushes
+int mh_fill_range_table_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* const traces[3], const uint64_t* public_values,
+                                     const uint64_t* aux_inputs, size_t n_aux_inputs, mh_range_table_info* info, uint64_t* n_written,
+                                     mh_balance_entry* entries, size_t entry_cap, size_t* n_entries, mh_balance_push* pushes, size_t push_cap,
+                                     size_t* n_pushes) {
+  if (!ctx || !m || m->ctx != ctx || !traces || !n_written || !n_entries || !n_pushes) return MH_ERR_INVALID;
+  mh_pcs_params prm;
+  mh_miden_pcs_params(&prm);
+  u64 pre[MH_MIDEN_PRE_OBSERVE_FELTS], state[12];
+  if (mh_miden_pre_observe(&prm, public_values, aux_inputs, n_aux_inputs, pre) != MH_OK) {
+    ctx->err = "mh_fill_range_table_miden_traces: 32 public values and aux inputs = program hash (4) | deferred root (4) | kernel digests (4 each, <= 255) expected";
+    return MH_ERR_INVALID;
+  }
+  mh_miden_challenger_state(state);
+  static const char* const names[3] = {"core", "chiplets", "poseidon2"};
+  static const mh_range_slot slot = {0, 0, 14, 50, 49};
+  auto boundary = [&](const std::vector<e2>& rnd, std::vector<BoundaryPush>& out) {
+    return rnd.size() >= 2 && boundary_pushes(Challenges(rnd[0], rnd[1]), aux_inputs, n_aux_inputs, out);
+  };
+  return range_statement(ctx, 3, m->airs, traces, nullptr, state, pre, MH_MIDEN_PRE_OBSERVE_FELTS, boundary, names, &slot, info, n_written,
+                         entries, entry_cap, n_entries, pushes, push_cap, n_pushes);
+}
 
 }  // extern "C"

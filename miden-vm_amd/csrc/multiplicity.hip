@@ -148,20 +148,15 @@ __global__ __launch_bounds__(BT) void k_mul_resolve(BalArgs a, MulArgs ma, MulRe
 }
 
 namespace {
-struct FillInput {
-  BalanceInput b;
-  mh_trace* main;  // the same trace, writable
-  int label;       // the caller's instance number (messages)
-};
-
 std::string slot_name(const FillInput& f, const char* const* names, u32 column, u32 fraction) {
   char buf[128];
   if (names) snprintf(buf, sizeof buf, "%s (instance %d) column %u fraction %u", names[f.label], f.label, column, fraction);
   else snprintf(buf, sizeof buf, "instance %d column %u fraction %u", f.label, column, fraction);
   return buf;
 }
+}  // namespace
 
-// slots[i].instance indexes `in`
+// slots[i].instance indexes `in` (balance.cuh: range_table.hip runs it as its last stage)
 void fill_run(mh_ctx* c, const std::vector<FillInput>& in, const std::vector<e2>& rnd, const std::vector<BoundaryPush>& boundary,
               const std::vector<mh_mult_slot>& slots, const char* const* names, u64* n_written, BalanceReport& rep) {
   const size_t n_in = in.size();
@@ -315,6 +310,7 @@ void fill_run(mh_ctx* c, const std::vector<FillInput>& in, const std::vector<e2>
   balance_run(c, bin, rnd, boundary, true, rep, &p0);
 }
 
+namespace {
 // the caller's slots -> instance = index into `in`; index_of[instance]: that index, or -1 (an AIR without a lookup program)
 std::vector<mh_mult_slot> fill_slots(mh_ctx* c, const std::vector<FillInput>& in, const std::vector<int>& index_of, const mh_mult_slot* slots,
                                      size_t n_slots) {
