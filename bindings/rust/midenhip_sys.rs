@@ -76,6 +76,30 @@ pub struct mh_p2_trace_info {
     pub defect_row: u64,
 }
 
+/// One memory access of mh_memory_section_build / mh_miden_memory_section, in program order (48 bytes).  kind: bit 0 = read, bit 1 =
+/// word access; addr is the element address; value: [0] for an element write, [0..3] for a word write, ignored by reads.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_mem_access {
+    pub ctx: u32,
+    pub addr: u32,
+    pub clk: u32,
+    pub kind: u32,
+    pub value: [u64; 4],
+}
+
+/// mh_memory_section_build / mh_miden_memory_section: what was written, or the defect that refused the list (see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_mem_section_info {
+    pub n_rows: u64,
+    pub n_words: u64,
+    pub n_contexts: u64,
+    pub log_n: i32,
+    pub defect: i32,
+    pub defect_index: u64,
+}
+
 /// An encoded denominator whose net multiplicity is not zero (mh_check_balance*; the reference's `Unmatched`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -457,4 +481,8 @@ unsafe extern "C" {
     // the range-check table laid on the device from the statement's lookups, in place (csrc/range_table.hip); info may be null
     pub fn mh_fill_range_table(ctx: *mut mh_ctx, n: c_int, lookups: *const *const mh_lookup, traces: *const *mut mh_trace, preprocessed: *const *const mh_trace, randomness: *const u64, n_randomness: usize, boundary_denoms: *const u64, boundary_signs: *const i32, n_boundary: usize, slot: *const mh_range_slot, info: *mut mh_range_table_info, n_written: *mut u64, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
     pub fn mh_fill_range_table_miden_traces(ctx: *mut mh_ctx, m: *const mh_miden, traces: *const *mut mh_trace, public_values: *const u64, aux_inputs: *const u64, n_aux_inputs: usize, info: *mut mh_range_table_info, n_written: *mut u64, entries: *mut mh_balance_entry, entry_cap: usize, n_entries: *mut usize, pushes: *mut mh_balance_push, push_cap: usize, n_pushes: *mut usize) -> c_int;
+    // the memory chiplet's trace section built on the device from an access list (csrc/memory_section.hip); row_of and info may be null
+    pub fn mh_memory_section_build(ctx: *mut mh_ctx, accesses: *const mh_mem_access, n: usize, log_n: c_int, out: *mut *mut mh_trace, row_of: *mut u32, info: *mut mh_mem_section_info) -> c_int;
+    pub fn mh_miden_memory_section(ctx: *mut mh_ctx, chiplets: *mut mh_trace, start_row: u64, accesses: *const mh_mem_access, n: usize, row_of: *mut u32, info: *mut mh_mem_section_info) -> c_int;
+    pub fn mh_memory_section_tile() -> u32;
 }

@@ -1045,6 +1045,58 @@ int mh_fill_range_table_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* c
                                      uint64_t* n_written, mh_balance_entry* entries, size_t entry_cap, size_t* n_entries,
                                      mh_balance_push* pushes, size_t push_cap, size_t* n_pushes);
 
+/* ---- the memory chiplet's trace section, built on the device from an access list -------------------------------------------------------
+ * The memory section of the chiplets trace is the one chiplet section that is not row-local: Memory::fill_trace (processor/src/trace/
+ * chiplets/memory/mod.rs:308-406, segment.rs) walks the accesses sorted by (context, word, clock), carries every word through its
+ * accesses, takes a delta against the previous row and inverts it.  Here the caller hands over the accesses in program order, 48 bytes
+ * each, and the device writes the 17 cells per access.  Device stage: csrc/memory_section.hip.  Every cell written is canonical.
+ *   row order   by (ctx, addr >> 2, clk); ties keep arrival order (a stable sort).
+ *   columns     rw (1 = read), ew (1 = word access), ctx, word_addr (addr & ~3), idx0, idx1 (the bits of addr & 3; 0 for a word
+ *               access), clk, v0..v3 (the word AFTER the access; a word nobody wrote is four zeros), d0, d1 (16-bit halves of the
+ *               delta), d_inv (its field inverse, 0 for delta 0), f_scw (1 when ctx and word equal the previous row's), w0, w1 (halves
+ *               of word_addr / 4).
+ *   delta       ctx difference when the context changed, else word_addr difference when the word changed, else clk difference.  Row 0
+ *               has delta 1 and f_scw 1: the reference starts from (ctx, word, clk - 1), for clk = 0 too.
+ * PRECONDITION: within one (ctx, word) the clocks do not decrease in arrival order (a processor emits accesses in clock order).  Then
+ * this is Memory::fill_trace cell for cell.  A list that breaks it is sorted by the rule above all the same.
+ * A DEFECT of the list: MH_ERR_INVALID, `info` filled, nothing written (*out = NULL), mh_last_error names kind and access; the context
+ * stays usable.  Kind 4 is decided on the host before anything else, kinds 1 and 2 in the first kernel (the lowest arrival index of
+ * either), kind 3 after the sort (the lowest arrival index):
+ *   1  kind > 3
+ *   2  a word access whose addr is not a multiple of 4 (UnalignedWordAccess)
+ *   3  two accesses of one (ctx, word) in one cycle of which the later is a write, or the earlier is a write (IllegalMemoryAccess);
+ *      defect_index = the later access
+ *   4  the section does not fit: n > 2^log_n, or start_row + n > the chiplets trace's height; defect_index = the first access
+ *      without a row
+ * n == 0 is MH_OK and writes no row.  n > 2^24, a null pointer, a chiplets trace that is not 22 wide or belongs to another context are
+ * refused before any launch.  `accesses` is a host pointer and may be reused when the call returns.  The call orders itself after a
+ * pending mh_trace_upload_async of the chiplets trace, waits twice (five words that fix the sort's digit plan and carry kinds 1 and 2;
+ * three words with kind 3 and the counts) and returns with the rows kernel enqueued on the context's stream; `row_of`, when asked for,
+ * costs a third wait.  Two calls on one input leave the same bytes and name the same defect.
+ * Not in scope: sharded contexts, device-resident access lists, the other four chiplet sections (hasher controller, bitwise, ACE,
+ * kernel ROM), lists whose clocks run against arrival order beyond the order rule stated above, and n > 2^24. */
+typedef struct mh_mem_access {      /* 48 bytes */
+  uint32_t ctx, addr, clk, kind;    /* kind: bit 0 = read, bit 1 = word access; addr is the ELEMENT address */
+  uint64_t value[4];                /* element write: value[0]; word write: value[0..3]; reads ignore it.  Any uint64_t, reduced mod p */
+} mh_mem_access;
+typedef struct mh_mem_section_info {
+  uint64_t n_rows;        /* rows written = n (0 when the call was refused) */
+  uint64_t n_words;       /* distinct (ctx, word) pairs */
+  uint64_t n_contexts;    /* distinct contexts */
+  int32_t  log_n;         /* height of the trace written to */
+  int32_t  defect;        /* 0, or the kind above */
+  uint64_t defect_index;  /* arrival index of the lowest offending access */
+} mh_mem_section_info;
+/* a trace of width 17 (MemoryCols + w0, w1), the section in rows [0, n), zeros below; log_n = -1: max(6, ceil log2 n) */
+int mh_memory_section_build(mh_ctx* ctx, const mh_mem_access* accesses, size_t n, int log_n, mh_trace** out,
+                            uint32_t* row_of /* [n] or NULL: the section row access i landed on */, mh_mem_section_info* info /* may be NULL */);
+/* the same rows written in place into a device-resident chiplets trace (width 22) at rows [start_row, start_row + n):
+ * columns 0..2 = 1, 1, 0 (the memory chiplet's selectors), columns 3..19 = the 17 cells; columns 20 and 21 are not touched */
+int mh_miden_memory_section(mh_ctx* ctx, mh_trace* chiplets, uint64_t start_row, const mh_mem_access* accesses, size_t n,
+                            uint32_t* row_of, mh_mem_section_info* info);
+/* rows of one tile of the word-carry scan (a property of the build; tests place their sizes around it) */
+uint32_t mh_memory_section_tile(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ EXPORTS = [
     "mh_check_balance", "mh_check_balance_miden", "mh_check_balance_miden_traces", "mh_check_balance_precompile", "mh_check_balance_precompile_traces",
     "mh_fill_multiplicities", "mh_fill_multiplicities_miden_traces", "mh_fill_multiplicities_precompile_traces",
     "mh_poseidon2_trace_build", "mh_miden_poseidon2_trace", "mh_fill_range_table", "mh_fill_range_table_miden_traces",
+    "mh_memory_section_build", "mh_miden_memory_section", "mh_memory_section_tile",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
@@ -322,6 +323,58 @@ def poseidon2_trace(ctx, states, multiplicities, log_n=None):
     t = Trace.from_handle(ctx, h, int(info.log_n), 16)
     t.p2_info = info
     return t
+
+
+# ---- the memory chiplet's trace section (include/midenhip.h mh_memory_section_build, mh_miden_memory_section) ----
+MEM_ACCESS_DTYPE = np.dtype([("ctx", "<u4"), ("addr", "<u4"), ("clk", "<u4"), ("kind", "<u4"), ("value", "<u8", (4,))])  # mh_mem_access
+MEM_READ, MEM_WORD = 1, 2  # mh_mem_access.kind bits
+
+
+class MemSectionInfo(C.Structure):
+    """mh_mem_section_info: n_rows rows written over n_words distinct (ctx, word) pairs in n_contexts contexts, into a trace of height
+    2^log_n; `defect` 0 none, 1 kind > 3, 2 unaligned word access, 3 two accesses of a word in one cycle with a write, 4 the section
+    does not fit; `defect_index` the arrival index of the lowest offending access."""
+    _fields_ = [("n_rows", C.c_uint64), ("n_words", C.c_uint64), ("n_contexts", C.c_uint64), ("log_n", C.c_int32), ("defect", C.c_int32),
+                ("defect_index", C.c_uint64)]
+
+    def __repr__(self):
+        return (f"MemSectionInfo(n_rows={self.n_rows}, n_words={self.n_words}, n_contexts={self.n_contexts}, log_n={self.log_n}, "
+                f"defect={self.defect}, defect_index={self.defect_index})")
+
+
+def _mem_accesses(accesses):
+    acc = np.ascontiguousarray(accesses, dtype=MEM_ACCESS_DTYPE).reshape(-1)
+    return acc, acc.ctypes.data_as(C.c_void_p) if acc.size else None
+
+
+def _mem_section_result(lib, ctx, rc, info):
+    if rc != 0:
+        e = MidenHipError(f"libmidenhip error {rc}: {lib.mh_last_error(ctx.h).decode()}")
+        e.info = info
+        raise e
+
+
+def memory_section_tile(lib=None):
+    """mh_memory_section_tile: rows of one tile of the word-carry scan."""
+    lib = lib or load_library()
+    lib.mh_memory_section_tile.restype = C.c_uint32
+    lib.mh_memory_section_tile.argtypes = []
+    return int(lib.mh_memory_section_tile())
+
+
+def memory_section(ctx, accesses, log_n=None, want_rows=False):
+    """mh_memory_section_build: Memory::fill_trace on the device from an access list in program order (MEM_ACCESS_DTYPE records; within a
+    word the clocks must not decrease) -> (Trace [2^log_n, 17], MemSectionInfo, row_of); log_n None: max(6, ceil log2 n).  row_of[i] is
+    the section row of access i (uint32 [n]) when want_rows, else None.  A defect of the list raises MidenHipError with `e.info`."""
+    acc, ap = _mem_accesses(accesses)
+    lib = ctx.lib
+    lib.mh_memory_section_build.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(MemSectionInfo)]
+    h, info = C.c_void_p(), MemSectionInfo()
+    rows = np.zeros(acc.size, dtype=np.uint32) if want_rows else None
+    rp = rows.ctypes.data_as(C.c_void_p) if want_rows and acc.size else None
+    rc = lib.mh_memory_section_build(ctx.h, ap, acc.size, -1 if log_n is None else int(log_n), C.byref(h), rp, C.byref(info))
+    _mem_section_result(lib, ctx, rc, info)
+    return Trace.from_handle(ctx, h, int(info.log_n), 17), info, rows
 
 
 def load_library():
@@ -1605,6 +1658,23 @@ class Miden:
             e.info = info
             raise e
         return Trace.from_handle(self.ctx, h, int(info.log_n), 16), info
+
+    def memory_section(self, chiplets, start_row, accesses, want_rows=False):
+        """mh_miden_memory_section: the memory chiplet's rows written in place into the device-resident chiplets Trace at rows
+        [start_row, start_row + n) from the access list (MEM_ACCESS_DTYPE records in program order): columns 0..2 = 1, 1, 0 and
+        columns 3..19; columns 20, 21 and every other row stay -> (MemSectionInfo, row_of or None).  A defect of the list, or a section
+        that does not fit, raises MidenHipError with `e.info`; nothing was written then."""
+        lib = self.ctx.lib
+        if not isinstance(chiplets, Trace):
+            raise MidenHipError("Miden.memory_section: a Trace object expected")
+        acc, ap = _mem_accesses(accesses)
+        lib.mh_miden_memory_section.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(MemSectionInfo)]
+        info = MemSectionInfo()
+        rows = np.zeros(acc.size, dtype=np.uint32) if want_rows else None
+        rp = rows.ctypes.data_as(C.c_void_p) if want_rows and acc.size else None
+        rc = lib.mh_miden_memory_section(self.ctx.h, chiplets.h, int(start_row), ap, acc.size, rp, C.byref(info))
+        _mem_section_result(lib, self.ctx, rc, info)
+        return info, rows
 
     def free(self):
         if getattr(self, "h", None) and self.ctx.h:

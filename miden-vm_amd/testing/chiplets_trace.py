@@ -153,12 +153,23 @@ class Memory:
     def __init__(self):
         self.trace = {}   # ctx -> {word_addr -> [(clk, is_read, is_word, idx, word)]}
         self.num_rows = 0
+        self.accesses = []   # (ctx, addr, clk, kind, value[4]) in call order, kind bit 0 = read, bit 1 = word: mh_mem_access
+
+    def _log(self, ctx, addr, clk, kind, value=(0, 0, 0, 0)):
+        self.accesses.append((int(ctx), int(addr), int(clk), kind, tuple(int(x) for x in value)))
+
+    def access_array(self):
+        """The calls made so far (a refused one included, as the last entry) as MEM_ACCESS_DTYPE records: the list
+        mh_memory_section_build takes."""
+        from .. import MEM_ACCESS_DTYPE
+        return np.array(self.accesses, dtype=MEM_ACCESS_DTYPE)
 
     def _addr_trace(self, ctx, addr):
         idx = addr % 4
         return self.trace.setdefault(int(ctx), {}).setdefault(addr - idx, []), idx
 
     def read(self, ctx, addr, clk):
+        self._log(ctx, addr, clk, 1)
         t, idx = self._addr_trace(ctx, int(addr))
         word = list(t[-1][4]) if t else [0, 0, 0, 0]
         assert not (t and t[-1][0] == clk and not t[-1][1]), "read after write in the same cycle"
@@ -167,6 +178,7 @@ class Memory:
         return word[idx]
 
     def read_word(self, ctx, addr, clk):
+        self._log(ctx, addr, clk, 3)
         assert addr % 4 == 0
         t, _ = self._addr_trace(ctx, int(addr))
         word = list(t[-1][4]) if t else [0, 0, 0, 0]
@@ -176,6 +188,7 @@ class Memory:
         return word
 
     def write(self, ctx, addr, clk, value):
+        self._log(ctx, addr, clk, 0, (value, 0, 0, 0))
         t, idx = self._addr_trace(ctx, int(addr))
         assert not (t and t[-1][0] == clk), "two accesses with a write in the same cycle"
         word = list(t[-1][4]) if t else [0, 0, 0, 0]
@@ -184,6 +197,7 @@ class Memory:
         self.num_rows += 1
 
     def write_word(self, ctx, addr, clk, word):
+        self._log(ctx, addr, clk, 2, word)
         assert addr % 4 == 0
         t, _ = self._addr_trace(ctx, int(addr))
         assert not (t and t[-1][0] == clk), "two accesses with a write in the same cycle"
