@@ -100,6 +100,40 @@ pub struct mh_mem_section_info {
     pub defect_index: u64,
 }
 
+/// One hash operation of mh_hasher_section_build / mh_miden_hasher_section, in program order (24 bytes).  kind: 0 permute, 1 control
+/// block, 2 basic block, 3 merkle verify, 4 merkle update; count: batches or depth; index: node index or domain; payload: offset of the
+/// operands in `felts`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_hash_op {
+    pub kind: u32,
+    pub count: u32,
+    pub index: u64,
+    pub payload: u64,
+}
+
+/// What one hash operation gave: the 1-based row of its first row, its last post-state, the old root of a merkle update.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_hash_result {
+    pub addr: u64,
+    pub state: [u64; 12],
+    pub old_root: [u64; 4],
+}
+
+/// mh_hasher_section_build / mh_miden_hasher_section: what was written, or the defect that refused the list (see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_hasher_section_info {
+    pub n_rows: u64,
+    pub n_permutations: u64,
+    pub n_requests: u64,
+    pub mrupdate_id: u64,
+    pub log_n: i32,
+    pub defect: i32,
+    pub defect_index: u64,
+}
+
 /// An encoded denominator whose net multiplicity is not zero (mh_check_balance*; the reference's `Unmatched`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -485,4 +519,8 @@ unsafe extern "C" {
     pub fn mh_memory_section_build(ctx: *mut mh_ctx, accesses: *const mh_mem_access, n: usize, log_n: c_int, out: *mut *mut mh_trace, row_of: *mut u32, info: *mut mh_mem_section_info) -> c_int;
     pub fn mh_miden_memory_section(ctx: *mut mh_ctx, chiplets: *mut mh_trace, start_row: u64, accesses: *const mh_mem_access, n: usize, row_of: *mut u32, info: *mut mh_mem_section_info) -> c_int;
     pub fn mh_memory_section_tile() -> u32;
+    // the hasher controller's trace section built on the device from an op list (csrc/hasher_section.hip); results and info may be null
+    pub fn mh_hasher_section_build(ctx: *mut mh_ctx, ops: *const mh_hash_op, n_ops: usize, felts: *const u64, n_felts: usize, log_n: c_int, out: *mut *mut mh_trace, results: *mut mh_hash_result, info: *mut mh_hasher_section_info) -> c_int;
+    pub fn mh_miden_hasher_section(ctx: *mut mh_ctx, chiplets: *mut mh_trace, ops: *const mh_hash_op, n_ops: usize, felts: *const u64, n_felts: usize, results: *mut mh_hash_result, info: *mut mh_hasher_section_info) -> c_int;
+    pub fn mh_hasher_section_tile() -> u32;
 }

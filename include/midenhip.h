@@ -1073,8 +1073,9 @@ int mh_fill_range_table_miden_traces(mh_ctx* ctx, const mh_miden* m, mh_trace* c
  * pending mh_trace_upload_async of the chiplets trace, waits twice (five words that fix the sort's digit plan and carry kinds 1 and 2;
  * three words with kind 3 and the counts) and returns with the rows kernel enqueued on the context's stream; `row_of`, when asked for,
  * costs a third wait.  Two calls on one input leave the same bytes and name the same defect.
- * Not in scope: sharded contexts, device-resident access lists, the other four chiplet sections (hasher controller, bitwise, ACE,
- * kernel ROM), lists whose clocks run against arrival order beyond the order rule stated above, and n > 2^24. */
+ * Not in scope: sharded contexts, device-resident access lists, the other four chiplet sections (of them bitwise, ACE and kernel ROM
+ * have no device builder; the hasher controller's is mh_hasher_section_build below), lists whose clocks run against arrival order
+ * beyond the order rule stated above, and n > 2^24. */
 typedef struct mh_mem_access {      /* 48 bytes */
   uint32_t ctx, addr, clk, kind;    /* kind: bit 0 = read, bit 1 = word access; addr is the ELEMENT address */
   uint64_t value[4];                /* element write: value[0]; word write: value[0..3]; reads ignore it.  Any uint64_t, reduced mod p */
@@ -1096,6 +1097,78 @@ int mh_miden_memory_section(mh_ctx* ctx, mh_trace* chiplets, uint64_t start_row,
                             uint32_t* row_of, mh_mem_section_info* info);
 /* rows of one tile of the word-carry scan (a property of the build; tests place their sizes around it) */
 uint32_t mh_memory_section_tile(void);
+
+/* ---- the hasher controller's trace section, built on the device from an op list --------------------------------------------------------
+ * The hasher controller is the first and largest chiplet section, and the one whose content is computed: every second row is a
+ * Poseidon2 output.  Hasher (processor/src/trace/chiplets/hasher/mod.rs:131-480, trace.rs:91-139) appends two rows per permutation
+ * and numbers the distinct pre-states in order of first appearance (record_perm_request).  Here the caller hands over the hash
+ * operations in program order, 24 bytes each plus their operands, and the device computes the permutations and writes the 20 cells per
+ * row.  Device stage: csrc/hasher_section.hip.  Every cell written is canonical.  With mh_miden_poseidon2_trace the third main trace
+ * follows from the same rows, so no permutation is computed on the host.
+ *   columns     sel[3] | state[12] | node_index | mrupdate_id | is_boundary | direction_bit | perm_id
+ *   rows        per permutation an input row (the op's selectors, the pre-state) and an output row (RETURN_HASH (0,0,0) or RETURN_STATE
+ *               (0,0,1), the post-state); both carry the permutation's perm_id and the mrupdate_id in effect.
+ *   permute           1 permutation, LINEAR_HASH (1,0,0) / RETURN_STATE, boundary 1 / 1
+ *   control block     state h1 | h2 | 0, domain, 0, 0; RETURN_HASH; boundary 1 / 1
+ *   basic block       a permutation per 8-felt batch: the rate is overwritten, the capacity kept (zero before the first); RETURN_STATE
+ *                     on all outputs but the last; boundary on the first input row and the last output row only
+ *   merkle verify     per level the state root | sibling, or sibling | root when the index's bit is 1, capacity zero; selectors MP_VERIFY
+ *                     (1,0,1); input row: the index and its lowest bit; output row: index >> 1 and the next level's bit (0 on the last
+ *                     level); boundary on level 0's input row and the last level's output row; RETURN_HASH on the last level only
+ *   merkle update     mrupdate_id += 1 first, then the old value's leg (MR_UPDATE_OLD (1,1,0)) and the new value's (MR_UPDATE_NEW (1,1,1))
+ *   perm_id     k for the k-th distinct pre-state in order of first appearance; distinct as canonical field elements (x and x + p are
+ *               one state); a repeat gets the first one's id.  n_requests is their number.
+ *   padding     to a multiple of 8 rows with selectors (0,1,0), all other cells 0 and mrupdate_id = the final counter
+ *   addr        of an op = the 1-based row of its first row
+ * A memoised replay of a block hash (replay_memoized_trace, mod.rs:404-431) appends the same rows under the current mrupdate_id and
+ * registers the same requests: for this interface it is simply the operation listed again.
+ * A DEFECT of the list: MH_ERR_INVALID, `info` filled, nothing written (*out = NULL), mh_last_error names kind and op; the context stays
+ * usable.  Every op is tested for kinds 1, 2, 3, 4 in this order and carries the first it has; the call reports the LOWEST op index that
+ * carries any of them -- the op at which the reference would stop -- so for each kind the lowest index with it when no earlier op is
+ * defective.  Kind 5 is reported only for a list without the others; it is known after the row-offset scan, before any row is written:
+ *   1  kind > 4
+ *   2  count out of range: a basic block with 0 batches, a Merkle depth of 0 or above 64 ("path is empty")
+ *   3  a Merkle index that is not below p, or with index >> depth != 0 for depth < 64 ("invalid index for the path")
+ *   4  operands that do not lie inside felts[0, n_felts)
+ *   5  the section does not fit: n_rows > 2^log_n, or n_rows above the chiplets trace's height; defect_index = the first op without its
+ *      rows (n_ops when only the padding lacks room)
+ * n_ops == 0 is MH_OK with zero rows.  A null pointer, a trace of the wrong width or of another context, log_n out of range and more than
+ * 2^24 permutations are refused without a defect number and before anything is written.  The permutation count of a list with n_ops <=
+ * 2^24 is known from the first kernels' read-back; it is tested before the defects and before any further launch, and every op counts
+ * with what its kind and count say (0 for defects 1 and 2).
+ * `ops`, `felts` and `results` are host pointers and may be reused when the call returns.  The call orders itself after a pending
+ * mh_trace_upload_async of the chiplets trace, runs on the context's stream and waits twice: for six words with the defects and the
+ * sizes, and for n_requests, which is part of `info` and known only when the chains have been walked.  It returns with the rows kernel
+ * enqueued; `results`, when asked for, costs a third wait.  Two calls on one input leave the same bytes and name the same defect.
+ * Not in scope: sharded contexts, device-resident op lists, the bitwise, ACE and kernel-ROM sections, deriving the op list from a program
+ * (the decoder's job), and the precompile prover's Poseidon2Air. */
+typedef struct mh_hash_op {     /* 24 bytes */
+  uint32_t kind;    /* 0 permute, 1 control block, 2 basic block, 3 merkle verify, 4 merkle update */
+  uint32_t count;   /* basic block: batches (>= 1); merkle: depth 1..64; otherwise ignored */
+  uint64_t index;   /* merkle: node index; control block: the domain felt; otherwise ignored */
+  uint64_t payload; /* offset, in felts, of this op's operands in `felts` */
+} mh_hash_op;
+/* operands: permute 12 (the state) | control block 8 (h1, h2) | basic block 8*count | merkle verify 4 + 4*depth (value, siblings from the
+   leaf up) | merkle update 8 + 4*depth (old value, new value, siblings).  Any uint64_t, reduced mod p. */
+typedef struct mh_hash_result { uint64_t addr; uint64_t state[12]; uint64_t old_root[4]; } mh_hash_result;
+/* addr = 1-based row of the op's first row; state = the op's last post-state (digest = state[0..3]; merkle update: of the NEW leg);
+   old_root = the old leg's root for a merkle update, zeros otherwise */
+typedef struct mh_hasher_section_info {
+  uint64_t n_rows;          /* controller rows incl. padding to a multiple of 8 (0 when refused) */
+  uint64_t n_permutations;  /* input rows */
+  uint64_t n_requests;      /* distinct pre-states = the k of mh_p2_trace_info */
+  uint64_t mrupdate_id;     /* final counter */
+  int32_t log_n, defect; uint64_t defect_index;
+} mh_hasher_section_info;
+/* a trace of width 20, the section in rows [0, n_rows), zeros below; log_n = -1: max(6, ceil log2 n_rows) */
+int mh_hasher_section_build(mh_ctx* ctx, const mh_hash_op* ops, size_t n_ops, const uint64_t* felts, size_t n_felts, int log_n,
+                            mh_trace** out /* width 20 */, mh_hash_result* results /* [n_ops] or NULL */, mh_hasher_section_info* info /* may be NULL */);
+/* the same rows written in place into rows [0, n_rows) of a device-resident chiplets trace (width 22; the hasher is always the first
+ * section): column 0 = 0, columns 1..20 = the 20 cells; column 21 (chip_clk) and every row from n_rows on are not touched */
+int mh_miden_hasher_section(mh_ctx* ctx, mh_trace* chiplets /* width 22 */, const mh_hash_op* ops, size_t n_ops, const uint64_t* felts,
+                            size_t n_felts, mh_hash_result* results, mh_hasher_section_info* info);
+/* ops (plan) and permutations (perm_id ranks) of one scan tile (a property of the build; tests place their sizes around it) */
+uint32_t mh_hasher_section_tile(void);
 
 #ifdef __cplusplus
 }

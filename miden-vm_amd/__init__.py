@@ -42,6 +42,7 @@ EXPORTS = [
     "mh_fill_multiplicities", "mh_fill_multiplicities_miden_traces", "mh_fill_multiplicities_precompile_traces",
     "mh_poseidon2_trace_build", "mh_miden_poseidon2_trace", "mh_fill_range_table", "mh_fill_range_table_miden_traces",
     "mh_memory_section_build", "mh_miden_memory_section", "mh_memory_section_tile",
+    "mh_hasher_section_build", "mh_miden_hasher_section", "mh_hasher_section_tile",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
@@ -375,6 +376,55 @@ def memory_section(ctx, accesses, log_n=None, want_rows=False):
     rc = lib.mh_memory_section_build(ctx.h, ap, acc.size, -1 if log_n is None else int(log_n), C.byref(h), rp, C.byref(info))
     _mem_section_result(lib, ctx, rc, info)
     return Trace.from_handle(ctx, h, int(info.log_n), 17), info, rows
+
+
+# ---- the hasher controller's trace section (include/midenhip.h mh_hasher_section_build, mh_miden_hasher_section) ----
+HASH_OP_DTYPE = np.dtype([("kind", "<u4"), ("count", "<u4"), ("index", "<u8"), ("payload", "<u8")])  # mh_hash_op
+HASH_RESULT_DTYPE = np.dtype([("addr", "<u8"), ("state", "<u8", (12,)), ("old_root", "<u8", (4,))])  # mh_hash_result
+HASH_PERMUTE, HASH_CONTROL_BLOCK, HASH_BASIC_BLOCK, HASH_MERKLE_VERIFY, HASH_MERKLE_UPDATE = range(5)  # mh_hash_op.kind
+
+
+class HasherSectionInfo(C.Structure):
+    """mh_hasher_section_info: n_rows controller rows (padding included) for n_permutations permutations with n_requests distinct
+    pre-states, the final mrupdate_id, into a trace of height 2^log_n; `defect` 0 none, 1 kind > 4, 2 count out of range, 3 invalid
+    Merkle index, 4 operands outside the felts, 5 the section does not fit; `defect_index` the lowest offending op."""
+    _fields_ = [("n_rows", C.c_uint64), ("n_permutations", C.c_uint64), ("n_requests", C.c_uint64), ("mrupdate_id", C.c_uint64),
+                ("log_n", C.c_int32), ("defect", C.c_int32), ("defect_index", C.c_uint64)]
+
+    def __repr__(self):
+        return (f"HasherSectionInfo(n_rows={self.n_rows}, n_permutations={self.n_permutations}, n_requests={self.n_requests}, "
+                f"mrupdate_id={self.mrupdate_id}, log_n={self.log_n}, defect={self.defect}, defect_index={self.defect_index})")
+
+
+def _hash_ops(ops, felts):
+    o = np.ascontiguousarray(ops, dtype=HASH_OP_DTYPE).reshape(-1)
+    f = np.ascontiguousarray(felts, dtype=np.uint64).reshape(-1)
+    return o, o.ctypes.data_as(C.c_void_p) if o.size else None, f, f.ctypes.data_as(C.c_void_p) if f.size else None
+
+
+def hasher_section_tile(lib=None):
+    """mh_hasher_section_tile: ops (and permutations) of one tile of the stage's scans."""
+    lib = lib or load_library()
+    lib.mh_hasher_section_tile.restype = C.c_uint32
+    lib.mh_hasher_section_tile.argtypes = []
+    return int(lib.mh_hasher_section_tile())
+
+
+def hasher_section(ctx, ops, felts, log_n=None, want_results=False):
+    """mh_hasher_section_build: the hasher controller's rows on the device from the hash operations in program order (HASH_OP_DTYPE
+    records whose `payload` points into `felts`, any uint64) -> (Trace [2^log_n, 20], HasherSectionInfo, results); log_n None:
+    max(6, ceil log2 n_rows).  results is a HASH_RESULT_DTYPE array (addr, last post-state, old root) when want_results, else None.
+    A defect of the list raises MidenHipError with `e.info`."""
+    o, op, f, fp = _hash_ops(ops, felts)
+    lib = ctx.lib
+    lib.mh_hasher_section_build.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p),
+                                            C.c_void_p, C.POINTER(HasherSectionInfo)]
+    h, info = C.c_void_p(), HasherSectionInfo()
+    res = np.zeros(o.size, dtype=HASH_RESULT_DTYPE) if want_results else None
+    rp = res.ctypes.data_as(C.c_void_p) if want_results and o.size else None
+    rc = lib.mh_hasher_section_build(ctx.h, op, o.size, fp, f.size, -1 if log_n is None else int(log_n), C.byref(h), rp, C.byref(info))
+    _mem_section_result(lib, ctx, rc, info)
+    return Trace.from_handle(ctx, h, int(info.log_n), 20), info, res
 
 
 def load_library():
@@ -1675,6 +1725,24 @@ class Miden:
         rc = lib.mh_miden_memory_section(self.ctx.h, chiplets.h, int(start_row), ap, acc.size, rp, C.byref(info))
         _mem_section_result(lib, self.ctx, rc, info)
         return info, rows
+
+    def hasher_section(self, chiplets, ops, felts, want_results=False):
+        """mh_miden_hasher_section: the hasher controller's rows written in place into rows [0, n_rows) of the device-resident chiplets
+        Trace from the op list (HASH_OP_DTYPE records in program order, operands in `felts`): column 0 = 0 and columns 1..20; column 21
+        and every row from n_rows on stay -> (HasherSectionInfo, results or None).  A defect of the list, or a section that does not
+        fit, raises MidenHipError with `e.info`; nothing was written then."""
+        lib = self.ctx.lib
+        if not isinstance(chiplets, Trace):
+            raise MidenHipError("Miden.hasher_section: a Trace object expected")
+        o, op, f, fp = _hash_ops(ops, felts)
+        lib.mh_miden_hasher_section.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                C.POINTER(HasherSectionInfo)]
+        info = HasherSectionInfo()
+        res = np.zeros(o.size, dtype=HASH_RESULT_DTYPE) if want_results else None
+        rp = res.ctypes.data_as(C.c_void_p) if want_results and o.size else None
+        rc = lib.mh_miden_hasher_section(self.ctx.h, chiplets.h, op, o.size, fp, f.size, rp, C.byref(info))
+        _mem_section_result(lib, self.ctx, rc, info)
+        return info, res
 
     def free(self):
         if getattr(self, "h", None) and self.ctx.h:

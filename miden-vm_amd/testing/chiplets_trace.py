@@ -10,7 +10,8 @@ What is restated (file:line of the reference):
   RESPAN batches, `build_merkle_root`, `update_merkle_root`, `append_controller_permutation`, `verify_merkle_path`, the
   permutation-request table with shared ids and multiplicities, padding to CONTROLLER_TRACE_ALIGNMENT = 8), rows
   hasher/trace.rs:214-277; selector constants air/src/trace/chiplets/hasher.rs:53-66.  (Memoised replays of a block hash,
-  hasher/mod.rs:404-431, produce the same rows as hashing it again; not modelled);
+  hasher/mod.rs:404-431, produce the same rows as hashing it again; not modelled: call the operation again.  `op_list()` gives the
+  calls made so far as the op list of mh_hasher_section_build);
 * bitwise: processor/src/trace/chiplets/bitwise/mod.rs:103-160 (8 rows per op, 4 bits per row from the most significant);
 * memory: processor/src/trace/chiplets/memory/mod.rs:225-330 and segment.rs (accesses sorted by ctx, word address, clock; the
   word after the operation; delta limbs; `d_inv`; `is_same_ctx_and_addr`; the two word-address limbs), range-check requests
@@ -43,6 +44,20 @@ class Hasher:
         self.rows = []            # (selectors, state, node_index, mrupdate_id, is_boundary, direction_bit, perm_id)
         self.perm_map, self.perm_requests = {}, []   # state -> id; [state, multiplicity]
         self.mrupdate_id = 0
+        self.ops = []             # (kind, count, index, operands) in call order: mh_hash_op and its felts
+
+    def _log(self, kind, count, index, operands):
+        self.ops.append((kind, int(count), int(index), [int(x) for x in operands]))
+
+    def op_list(self):
+        """The calls made so far as (ops, felts): HASH_OP_DTYPE records in call order whose `payload` points into the uint64 array
+        `felts` -- the list mh_hasher_section_build takes."""
+        from .. import HASH_OP_DTYPE
+        ops, felts = np.zeros(len(self.ops), dtype=HASH_OP_DTYPE), []
+        for i, (kind, count, index, operands) in enumerate(self.ops):
+            ops[i] = (kind, count, index, len(felts))
+            felts.extend(operands)
+        return ops, np.array(felts, dtype=np.uint64)
 
     def next_row_addr(self):
         return len(self.rows) + 1
@@ -65,16 +80,19 @@ class Hasher:
         return out
 
     def permute(self, state):                                            # HPERM
+        self._log(0, 0, 0, state)
         addr = self.next_row_addr()
         return addr, self._append_permutation(LINEAR_HASH, RETURN_STATE, state, 0, 0, 1, 1, 0, 0)
 
     def hash_control_block(self, h1, h2, domain):
+        self._log(1, 0, domain, list(h1) + list(h2))
         addr = self.next_row_addr()
         out = self._append_permutation(LINEAR_HASH, RETURN_HASH, list(h1) + list(h2) + [0, domain, 0, 0], 0, 0, 1, 1, 0, 0)
         return addr, out[0:4]
 
     def hash_basic_block(self, batches):
         """`batches`: the 8-felt op-group words of the block's op batches (one permutation each, RESPAN between them)."""
+        self._log(2, len(batches), 0, [x for b in batches for x in b])
         addr = self.next_row_addr()
         st = list(batches[0]) + [0, 0, 0, 0]
         if len(batches) == 1:
@@ -99,10 +117,12 @@ class Hasher:
         return root
 
     def build_merkle_root(self, value, path, index):                      # MPVERIFY
+        self._log(3, len(path), index, list(value) + [x for sib in path for x in sib])
         addr = self.next_row_addr()
         return addr, self._verify_merkle_path(value, path, index, MP_VERIFY)
 
     def update_merkle_root(self, old_value, new_value, path, index):      # MRUPDATE
+        self._log(4, len(path), index, list(old_value) + list(new_value) + [x for sib in path for x in sib])
         self.mrupdate_id += 1
         addr = self.next_row_addr()
         old_root = self._verify_merkle_path(old_value, path, index, MR_UPDATE_OLD)
