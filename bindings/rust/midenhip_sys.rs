@@ -134,6 +134,106 @@ pub struct mh_hasher_section_info {
     pub defect_index: u64,
 }
 
+/// One bitwise operation of mh_bitwise_section_build / mh_miden_bitwise_section, in program order (12 bytes).  op: 0 AND, 1 XOR.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_bitwise_op {
+    pub op: u32,
+    pub a: u32,
+    pub b: u32,
+}
+
+/// mh_bitwise_section_build / mh_miden_bitwise_section: what was written, or the defect that refused the list (see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_bitwise_section_info {
+    pub n_rows: u64,
+    pub log_n: i32,
+    pub defect: i32,
+    pub defect_index: u64,
+}
+
+/// One circuit evaluation of mh_ace_section_build / mh_miden_ace_section, in clock order (32 bytes).  payload: offset in `felts` of
+/// 2 * num_vars felts (the words as read from memory) followed by num_eval instruction felts.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_ace_eval {
+    pub ctx: u32,
+    pub ptr: u32,
+    pub clk: u32,
+    pub num_vars: u32,
+    pub num_eval: u32,
+    pub reserved: u32,
+    pub payload: u64,
+}
+
+/// mh_ace_section_build / mh_miden_ace_section: what was written, or the defect that refused the list (see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_ace_section_info {
+    pub n_rows: u64,
+    pub n_wires: u64,
+    pub n_gates: u64,
+    pub n_rounds: u64,
+    pub log_n: i32,
+    pub defect: i32,
+    pub defect_index: u64,
+    pub defect_gate: u64,
+}
+
+/// mh_kernel_rom_section_build / mh_miden_kernel_rom_section: what was written, or the defect that refused the lists (see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_kernel_rom_section_info {
+    pub n_rows: u64,
+    pub n_calls: u64,
+    pub log_n: i32,
+    pub defect: i32,
+    pub defect_index: u64,
+}
+
+/// The five lists of one executed program (mh_miden_chiplets_build): host pointers and counts.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct mh_chiplets_lists {
+    pub hash_ops: *const mh_hash_op,
+    pub n_hash_ops: usize,
+    pub hash_felts: *const u64,
+    pub n_hash_felts: usize,
+    pub bitwise_ops: *const mh_bitwise_op,
+    pub n_bitwise_ops: usize,
+    pub mem_accesses: *const mh_mem_access,
+    pub n_mem_accesses: usize,
+    pub ace_evals: *const mh_ace_eval,
+    pub n_ace_evals: usize,
+    pub ace_felts: *const u64,
+    pub n_ace_felts: usize,
+    pub kernel_procs: *const u64,
+    pub n_kernel_procs: usize,
+    pub kernel_calls: *const u64,
+    pub n_kernel_calls: usize,
+}
+
+/// mh_miden_chiplets_build: the section starts, the trace length, the first defective section (-1 none, 0 hasher .. 4 kernel ROM,
+/// 5 the frame) and the five builders' infos.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_chiplets_info {
+    pub start: [u64; 5],
+    pub padding_start: u64,
+    pub trace_len: u64,
+    pub log_n: i32,
+    pub defect_section: i32,
+    pub defect: i32,
+    pub reserved: i32,
+    pub defect_index: u64,
+    pub hasher: mh_hasher_section_info,
+    pub bitwise: mh_bitwise_section_info,
+    pub memory: mh_mem_section_info,
+    pub ace: mh_ace_section_info,
+    pub kernel_rom: mh_kernel_rom_section_info,
+}
+
 /// An encoded denominator whose net multiplicity is not zero (mh_check_balance*; the reference's `Unmatched`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -523,4 +623,15 @@ unsafe extern "C" {
     pub fn mh_hasher_section_build(ctx: *mut mh_ctx, ops: *const mh_hash_op, n_ops: usize, felts: *const u64, n_felts: usize, log_n: c_int, out: *mut *mut mh_trace, results: *mut mh_hash_result, info: *mut mh_hasher_section_info) -> c_int;
     pub fn mh_miden_hasher_section(ctx: *mut mh_ctx, chiplets: *mut mh_trace, ops: *const mh_hash_op, n_ops: usize, felts: *const u64, n_felts: usize, results: *mut mh_hash_result, info: *mut mh_hasher_section_info) -> c_int;
     pub fn mh_hasher_section_tile() -> u32;
+    // the bitwise, ACE and kernel-ROM sections and the whole chiplets trace built on the device (csrc/bitwise_section.hip, ace_section.hip,
+    // kernel_rom_section.hip, chiplets_build.hip); results, digests and info may be null
+    pub fn mh_bitwise_section_build(ctx: *mut mh_ctx, ops: *const mh_bitwise_op, n_ops: usize, log_n: c_int, out: *mut *mut mh_trace, results: *mut u32, info: *mut mh_bitwise_section_info) -> c_int;
+    pub fn mh_miden_bitwise_section(ctx: *mut mh_ctx, chiplets: *mut mh_trace, start_row: u64, ops: *const mh_bitwise_op, n_ops: usize, results: *mut u32, info: *mut mh_bitwise_section_info) -> c_int;
+    pub fn mh_ace_section_build(ctx: *mut mh_ctx, evals: *const mh_ace_eval, n_evals: usize, felts: *const u64, n_felts: usize, log_n: c_int, out: *mut *mut mh_trace, info: *mut mh_ace_section_info) -> c_int;
+    pub fn mh_miden_ace_section(ctx: *mut mh_ctx, chiplets: *mut mh_trace, start_row: u64, evals: *const mh_ace_eval, n_evals: usize, felts: *const u64, n_felts: usize, info: *mut mh_ace_section_info) -> c_int;
+    pub fn mh_ace_section_tile() -> u32;
+    pub fn mh_kernel_rom_section_build(ctx: *mut mh_ctx, procs: *const u64, n_procs: usize, calls: *const u64, n_calls: usize, log_n: c_int, out: *mut *mut mh_trace, digests: *mut u64, info: *mut mh_kernel_rom_section_info) -> c_int;
+    pub fn mh_miden_kernel_rom_section(ctx: *mut mh_ctx, chiplets: *mut mh_trace, start_row: u64, procs: *const u64, n_procs: usize, calls: *const u64, n_calls: usize, digests: *mut u64, info: *mut mh_kernel_rom_section_info) -> c_int;
+    pub fn mh_miden_chiplets_build(ctx: *mut mh_ctx, lists: *const mh_chiplets_lists, log_n: c_int, out: *mut *mut mh_trace, info: *mut mh_chiplets_info) -> c_int;
+    pub fn mh_miden_chiplets_frame(ctx: *mut mh_ctx, chiplets: *mut mh_trace, padding_start: u64) -> c_int;
 }

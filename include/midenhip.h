@@ -1170,6 +1170,148 @@ int mh_miden_hasher_section(mh_ctx* ctx, mh_trace* chiplets /* width 22 */, cons
 /* ops (plan) and permutations (perm_id ranks) of one scan tile (a property of the build; tests place their sizes around it) */
 uint32_t mh_hasher_section_tile(void);
 
+/* ---- the bitwise, ACE and kernel-ROM sections, and the whole chiplets trace, built on the device --------------------------------------
+ * The three chiplet sections the two builders above leave out, and one entry that takes the five lists of an executed program and
+ * returns the finished device-resident chiplets trace: no chiplets cell is uploaded.  Device stages: csrc/bitwise_section.hip,
+ * csrc/ace_section.hip, csrc/kernel_rom_section.hip, csrc/chiplets_build.hip.  Every cell written is canonical, every cell has one
+ * writer, and two calls on one input leave the same bytes and name the same defect.  All list pointers are host pointers and may be
+ * reused when a call returns.  A DEFECT of a list: MH_ERR_INVALID, `info` filled, nothing written (*out = NULL), mh_last_error names
+ * kind and index; the context stays usable.  A null pointer, a chiplets trace that is not 22 wide or belongs to another context and a
+ * log_n outside 6..32 (other than -1) are refused without a defect number.  Each builder has a standalone form (a trace of the section's
+ * own width, the section in rows [0, n_rows), zeros below; log_n = -1: max(6, ceil log2 n_rows)) and an in-place form that writes rows
+ * [start_row, start_row + n_rows) of a width-22 chiplets trace: the section's selector prefix and its payload columns, nothing else.
+ *
+ * BITWISE (processor/src/trace/chiplets/bitwise/mod.rs): 13 columns, 8 rows per operation.  Row i = 0..7 with off = 28 - 4i holds
+ *   op | a >> off | b >> off | the four low bits of a >> off, LSB first | those of b >> off | prev | result
+ * where result = prev << 4 | the row's result nibble and prev is the result of the row before (0 on row 0).  In place: columns 0, 1 =
+ * 1, 0 and columns 2..14.  Defects, in this order:
+ *   1  op > 1; defect_index = the lowest such op.  Decided by one pass over the list on the host before any launch.
+ *   2  the section does not fit: 8 n_ops > 2^log_n or beyond the chiplets trace's height; defect_index = the first op without its rows.
+ * More than 2^24 rows are refused before any launch.  One kernel, no wait; `results` (a AND b / a XOR b per op), when asked for, is
+ * written by the same kernel and costs one wait.
+ *
+ * ACE (ace/{mod,trace,instruction}.rs, execution/operations/eval_circuit.rs:54-118): 16 columns.  One evaluation has n_read =
+ * num_vars / 2 READ rows and num_eval EVAL rows and nw = 2 n_read + num_eval wires whose ids descend from nw - 1 in insertion order.
+ *   READ row i   s_start = (i == 0) | 0 | ctx | ptr + 4i | clk | 0 | id0 = nw-1-2i | v0 (word[0], word[1]) | id1 = id0 - 1 | v1 (word[2],
+ *                word[3]) | num_eval - 1 | 0 | m1 | m0
+ *   EVAL row k   0 | 1 | ctx | ptr + 4 n_read + k | clk | eval_op (p-1 sub, 0 mul, 1 add) | id0 = num_eval-1-k | v0 | id_l | v_l | id_r |
+ *                v_r | m0
+ * An instruction is id_l | id_r << 30 | op << 60 of the canonical felt (op 0 sub, 1 mul, 2 add); m of a wire is the number of times any
+ * gate of the evaluation names it (id_l == id_r counts twice); products are in F_p[x]/(x^2 - 7); the last wire must be zero.  The
+ * operands of evaluation e lie at felts[payload ..]: 2 num_vars felts (the n_read words as read from memory), then num_eval instruction
+ * felts.  Evaluations are listed in clock order, which is the reference's row order.  In place: columns 0..3 = 1, 1, 1, 0 and columns
+ * 4..19.  Every evaluation is tested for kinds 1, 2, 3, 4 in this order and carries the first it has; the call reports the LOWEST
+ * evaluation that carries any of them, then kind 5, then kind 6 for the lowest evaluation with it:
+ *   1  num_vars zero or odd, num_eval zero or not a multiple of 4, or more than 2^30 - 1 wires
+ *   2  clk not above the previous evaluation's
+ *   3  operands that do not lie inside felts[0, n_felts), or ptr + 2 num_vars + num_eval beyond the 32-bit address space
+ *   4  a gate whose opcode is above 2 or that names a wire not yet inserted (the gate itself included); defect_gate = the lowest such
+ *      gate of that evaluation
+ *   5  the section does not fit; defect_index = the first evaluation without its rows
+ *   6  the circuit does not evaluate to zero.  Known only after evaluation: the rows kernel is enqueued after that read-back.
+ * More than 2^24 rows (by the headers as they stand) are refused before any launch.  The call waits twice: for the words with kinds
+ * 1..5 and the sizes, and for kind 6 and n_rounds; it returns with the rows kernel enqueued.
+ * Evaluation: a wave takes one evaluation and walks its gates 64 at a time, a lane a gate.  In a round every gate whose operands lie
+ * before the window or belong to a finished lane of the window computes; finished values pass between lanes inside the wave.  n_rounds
+ * is the total of rounds over all windows of all evaluations, a function of the circuits alone: a chain of N gates of which each
+ * reads the one before costs N, N gates that read only READ wires cost ceil(N / 64).
+ *
+ * KERNEL ROM (kernel_rom/mod.rs): 5 columns m | h0..h3, one row per DISTINCT declared procedure digest (declared duplicates collapse,
+ * as the reference's map does), sorted by the 32 canonical little-endian bytes of the four felts compared lexicographically -- not
+ * numeric order: 0x0100 sorts before 0x0001.  m = the number of calls of that digest.  Digests are any uint64_t, reduced mod p.  In
+ * place: columns 0..4 = 1, 1, 1, 1, 0 and columns 5..9.  n_procs > 255 is refused without a defect number.  Defects, in this order:
+ *   1  a call of an undeclared digest (SyscallTargetNotInKernel); defect_index = the lowest such call
+ *   2  the section does not fit; defect_index = the first row without room
+ * One wait (the row count and kind 1); `digests` (the rows' digests in trace order: what the caller puts into aux_inputs[8..]), when
+ * asked for, costs a second.
+ *
+ * FRAME and WHOLE TRACE (trace/chiplets/mod.rs:58-73, 134-173, 213-310).  Width 22; trace_len = hasher rows (a multiple of 8) + 8 *
+ * bitwise ops + memory accesses + ACE rows + kernel rows + 1: one padding row is mandatory.
+ *   section     selector prefix    payload columns
+ *   hasher      s0 = 0             1..20
+ *   bitwise     (1,0)              2..14
+ *   memory      (1,1,0)            3..19
+ *   ACE         (1,1,1,0)          4..19
+ *   kernel ROM  (1,1,1,1,0)        5..9
+ *   padding     (1,1,1,1,1)        zero payload
+ * Column 21 is row + 1 on every row; every cell no section owns is 0.  mh_miden_chiplets_frame writes column 21 on all rows and, from
+ * padding_start on, ones in columns 0..4 and zeros in columns 5..20; it touches nothing else and does not wait.
+ * mh_miden_chiplets_build allocates the trace on the device (log_n = -1: max(6, ceil log2 trace_len)), zero-fills it, runs the five
+ * in-place builders in trace order at the starts it computes and writes the frame; no matrix is uploaded.  The sizes are known before
+ * the allocation: the hasher's, bitwise, memory and ACE rows from the lists' headers as they stand (a defective op counts with what
+ * its kind and count say, 0 for an unknown kind), the kernel rows from a first run of the kernel-ROM sort (one wait, skipped for
+ * fewer than two procedures).  trace_len > 2^log_n is a defect of its own (defect_section 5, defect 1, defect_index = trace_len),
+ * reported before anything is allocated.  Otherwise a defect in any list frees the trace (*out = NULL) and the report names the first
+ * defective section in trace order (defect_section 0 hasher .. 4 kernel ROM; defect and defect_index as that section's builder gives
+ * them; the section's own info holds the rest).  An empty list is legal and takes no rows.  Everything is ordered on the context's
+ * stream, and the call waits up to 8 times: 1 for the kernel row count, 2 in the hasher builder, 0 in the bitwise builder, 2 in the
+ * memory builder, 2 in the ACE builder, 1 in the kernel-ROM builder; it returns with the frame kernel enqueued.
+ * Not in scope: sharded contexts, device-resident lists, deriving the lists from a program, emitting the memory accesses an evaluation
+ * makes (the caller's memory list already holds them), and the precompile prover's chiplets. */
+typedef struct mh_bitwise_op { uint32_t op, a, b; } mh_bitwise_op;   /* 12 bytes; op 0 AND, 1 XOR */
+typedef struct mh_bitwise_section_info {
+  uint64_t n_rows;        /* 8 n_ops (0 when refused) */
+  int32_t log_n, defect; uint64_t defect_index;
+} mh_bitwise_section_info;
+int mh_bitwise_section_build(mh_ctx* ctx, const mh_bitwise_op* ops, size_t n_ops, int log_n, mh_trace** out /* width 13 */,
+                             uint32_t* results /* [n_ops] or NULL */, mh_bitwise_section_info* info /* may be NULL */);
+int mh_miden_bitwise_section(mh_ctx* ctx, mh_trace* chiplets /* width 22 */, uint64_t start_row, const mh_bitwise_op* ops, size_t n_ops,
+                             uint32_t* results, mh_bitwise_section_info* info);
+
+typedef struct mh_ace_eval {       /* 32 bytes */
+  uint32_t ctx, ptr, clk, num_vars, num_eval, reserved;
+  uint64_t payload;                /* offset, in felts, of this evaluation's operands in `felts` */
+} mh_ace_eval;
+typedef struct mh_ace_section_info {
+  uint64_t n_rows;        /* READ + EVAL rows (0 when refused) */
+  uint64_t n_wires, n_gates;
+  uint64_t n_rounds;      /* see "Evaluation" above; 0 until the circuits have been evaluated */
+  int32_t log_n, defect;
+  uint64_t defect_index;  /* the evaluation */
+  uint64_t defect_gate;   /* kind 4: the gate; otherwise 0 */
+} mh_ace_section_info;
+int mh_ace_section_build(mh_ctx* ctx, const mh_ace_eval* evals, size_t n_evals, const uint64_t* felts, size_t n_felts, int log_n,
+                         mh_trace** out /* width 16 */, mh_ace_section_info* info /* may be NULL */);
+int mh_miden_ace_section(mh_ctx* ctx, mh_trace* chiplets /* width 22 */, uint64_t start_row, const mh_ace_eval* evals, size_t n_evals,
+                         const uint64_t* felts, size_t n_felts, mh_ace_section_info* info);
+/* evaluations of one tile of the plan's scan (a property of the build; tests place their sizes around it) */
+uint32_t mh_ace_section_tile(void);
+
+typedef struct mh_kernel_rom_section_info {
+  uint64_t n_rows;        /* distinct declared digests (0 when refused) */
+  uint64_t n_calls;
+  int32_t log_n, defect; uint64_t defect_index;
+} mh_kernel_rom_section_info;
+int mh_kernel_rom_section_build(mh_ctx* ctx, const uint64_t* procs /* [n_procs][4] */, size_t n_procs, const uint64_t* calls /* [n_calls][4] */,
+                                size_t n_calls, int log_n, mh_trace** out /* width 5 */, uint64_t* digests /* [n_procs][4] or NULL: the first
+                                n_rows entries are written, in trace order */, mh_kernel_rom_section_info* info /* may be NULL */);
+int mh_miden_kernel_rom_section(mh_ctx* ctx, mh_trace* chiplets /* width 22 */, uint64_t start_row, const uint64_t* procs, size_t n_procs,
+                                const uint64_t* calls, size_t n_calls, uint64_t* digests, mh_kernel_rom_section_info* info);
+
+typedef struct mh_chiplets_lists {
+  const mh_hash_op* hash_ops; size_t n_hash_ops; const uint64_t* hash_felts; size_t n_hash_felts;
+  const mh_bitwise_op* bitwise_ops; size_t n_bitwise_ops;
+  const mh_mem_access* mem_accesses; size_t n_mem_accesses;
+  const mh_ace_eval* ace_evals; size_t n_ace_evals; const uint64_t* ace_felts; size_t n_ace_felts;
+  const uint64_t* kernel_procs; size_t n_kernel_procs; const uint64_t* kernel_calls; size_t n_kernel_calls;
+} mh_chiplets_lists;
+typedef struct mh_chiplets_info {
+  uint64_t start[5];        /* first row of the hasher, bitwise, memory, ACE and kernel-ROM sections */
+  uint64_t padding_start, trace_len;   /* trace_len = padding_start + 1 */
+  int32_t log_n;
+  int32_t defect_section;   /* -1, or 0 hasher .. 4 kernel ROM, 5 the frame (trace_len > 2^log_n) */
+  int32_t defect, reserved;
+  uint64_t defect_index;
+  mh_hasher_section_info hasher;
+  mh_bitwise_section_info bitwise;
+  mh_mem_section_info memory;
+  mh_ace_section_info ace;
+  mh_kernel_rom_section_info kernel_rom;
+} mh_chiplets_info;
+int mh_miden_chiplets_build(mh_ctx* ctx, const mh_chiplets_lists* lists, int log_n, mh_trace** out /* width 22 */,
+                            mh_chiplets_info* info /* may be NULL */);
+int mh_miden_chiplets_frame(mh_ctx* ctx, mh_trace* chiplets /* width 22 */, uint64_t padding_start);
+
 #ifdef __cplusplus
 }
 #endif

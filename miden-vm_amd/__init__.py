@@ -43,6 +43,8 @@ EXPORTS = [
     "mh_poseidon2_trace_build", "mh_miden_poseidon2_trace", "mh_fill_range_table", "mh_fill_range_table_miden_traces",
     "mh_memory_section_build", "mh_miden_memory_section", "mh_memory_section_tile",
     "mh_hasher_section_build", "mh_miden_hasher_section", "mh_hasher_section_tile",
+    "mh_bitwise_section_build", "mh_miden_bitwise_section", "mh_ace_section_build", "mh_miden_ace_section", "mh_ace_section_tile",
+    "mh_kernel_rom_section_build", "mh_miden_kernel_rom_section", "mh_miden_chiplets_build", "mh_miden_chiplets_frame",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
@@ -425,6 +427,144 @@ def hasher_section(ctx, ops, felts, log_n=None, want_results=False):
     rc = lib.mh_hasher_section_build(ctx.h, op, o.size, fp, f.size, -1 if log_n is None else int(log_n), C.byref(h), rp, C.byref(info))
     _mem_section_result(lib, ctx, rc, info)
     return Trace.from_handle(ctx, h, int(info.log_n), 20), info, res
+
+
+# ---- the bitwise, ACE and kernel-ROM sections and the whole chiplets trace (include/midenhip.h mh_bitwise_section_build ..
+# mh_miden_chiplets_build) ----
+BITWISE_OP_DTYPE = np.dtype([("op", "<u4"), ("a", "<u4"), ("b", "<u4")])  # mh_bitwise_op
+ACE_EVAL_DTYPE = np.dtype([("ctx", "<u4"), ("ptr", "<u4"), ("clk", "<u4"), ("num_vars", "<u4"), ("num_eval", "<u4"), ("reserved", "<u4"),
+                           ("payload", "<u8")])  # mh_ace_eval
+BITWISE_AND, BITWISE_XOR = 0, 1  # mh_bitwise_op.op
+
+
+class BitwiseSectionInfo(C.Structure):
+    """mh_bitwise_section_info: n_rows = 8 n_ops rows into a trace of height 2^log_n; `defect` 0 none, 1 op > 1, 2 the section does not
+    fit; `defect_index` the lowest offending op."""
+    _fields_ = [("n_rows", C.c_uint64), ("log_n", C.c_int32), ("defect", C.c_int32), ("defect_index", C.c_uint64)]
+
+    def __repr__(self):
+        return f"BitwiseSectionInfo(n_rows={self.n_rows}, log_n={self.log_n}, defect={self.defect}, defect_index={self.defect_index})"
+
+
+class AceSectionInfo(C.Structure):
+    """mh_ace_section_info: n_rows READ and EVAL rows over n_wires wires and n_gates gates, evaluated in n_rounds rounds; `defect` 0
+    none, 1 bad num_vars / num_eval, 2 clk not above the previous evaluation's, 3 operands outside the felts or the address space, 4 a
+    bad gate (`defect_gate`), 5 the section does not fit, 6 the circuit does not evaluate to zero; `defect_index` the evaluation."""
+    _fields_ = [("n_rows", C.c_uint64), ("n_wires", C.c_uint64), ("n_gates", C.c_uint64), ("n_rounds", C.c_uint64), ("log_n", C.c_int32),
+                ("defect", C.c_int32), ("defect_index", C.c_uint64), ("defect_gate", C.c_uint64)]
+
+    def __repr__(self):
+        return (f"AceSectionInfo(n_rows={self.n_rows}, n_wires={self.n_wires}, n_gates={self.n_gates}, n_rounds={self.n_rounds}, "
+                f"log_n={self.log_n}, defect={self.defect}, defect_index={self.defect_index}, defect_gate={self.defect_gate})")
+
+
+class KernelRomSectionInfo(C.Structure):
+    """mh_kernel_rom_section_info: n_rows distinct declared digests, n_calls calls; `defect` 0 none, 1 a call of an undeclared digest,
+    2 the section does not fit; `defect_index` the lowest offending call (1) or the first row without room (2)."""
+    _fields_ = [("n_rows", C.c_uint64), ("n_calls", C.c_uint64), ("log_n", C.c_int32), ("defect", C.c_int32), ("defect_index", C.c_uint64)]
+
+    def __repr__(self):
+        return (f"KernelRomSectionInfo(n_rows={self.n_rows}, n_calls={self.n_calls}, log_n={self.log_n}, defect={self.defect}, "
+                f"defect_index={self.defect_index})")
+
+
+class ChipletsLists(C.Structure):
+    """mh_chiplets_lists: the five lists of one executed program (host pointers and counts)."""
+    _fields_ = [("hash_ops", C.c_void_p), ("n_hash_ops", C.c_size_t), ("hash_felts", C.c_void_p), ("n_hash_felts", C.c_size_t),
+                ("bitwise_ops", C.c_void_p), ("n_bitwise_ops", C.c_size_t), ("mem_accesses", C.c_void_p), ("n_mem_accesses", C.c_size_t),
+                ("ace_evals", C.c_void_p), ("n_ace_evals", C.c_size_t), ("ace_felts", C.c_void_p), ("n_ace_felts", C.c_size_t),
+                ("kernel_procs", C.c_void_p), ("n_kernel_procs", C.c_size_t), ("kernel_calls", C.c_void_p), ("n_kernel_calls", C.c_size_t)]
+
+
+class ChipletsInfo(C.Structure):
+    """mh_chiplets_info: the section starts (hasher, bitwise, memory, ACE, kernel ROM), padding_start, trace_len = padding_start + 1,
+    log_n; `defect_section` -1 none, 0..4 the first defective section in trace order, 5 the frame (trace_len > 2^log_n), with that
+    section's `defect` and `defect_index`; then the five builders' infos."""
+    _fields_ = [("start", C.c_uint64 * 5), ("padding_start", C.c_uint64), ("trace_len", C.c_uint64), ("log_n", C.c_int32),
+                ("defect_section", C.c_int32), ("defect", C.c_int32), ("reserved", C.c_int32), ("defect_index", C.c_uint64),
+                ("hasher", HasherSectionInfo), ("bitwise", BitwiseSectionInfo), ("memory", MemSectionInfo), ("ace", AceSectionInfo),
+                ("kernel_rom", KernelRomSectionInfo)]
+
+    def __repr__(self):
+        return (f"ChipletsInfo(start={list(self.start)}, padding_start={self.padding_start}, trace_len={self.trace_len}, log_n={self.log_n}, "
+                f"defect_section={self.defect_section}, defect={self.defect}, defect_index={self.defect_index})")
+
+
+def _records(x, dtype):
+    """a contiguous 1-d array of `dtype` records; an empty sequence is an empty list"""
+    return np.ascontiguousarray(x, dtype=dtype).reshape(-1) if len(x) else np.zeros(0, dtype=dtype)
+
+
+def _bitwise_ops(ops):
+    o = _records(ops, BITWISE_OP_DTYPE)
+    return o, o.ctypes.data_as(C.c_void_p) if o.size else None
+
+
+def _ace_evals(evals, felts):
+    e = _records(evals, ACE_EVAL_DTYPE)
+    f = np.ascontiguousarray(felts, dtype=np.uint64).reshape(-1)
+    return e, e.ctypes.data_as(C.c_void_p) if e.size else None, f, f.ctypes.data_as(C.c_void_p) if f.size else None
+
+
+def _digests(d):
+    a = np.ascontiguousarray(d, dtype=np.uint64).reshape(-1, 4)
+    return a, a.ctypes.data_as(C.c_void_p) if a.size else None
+
+
+def ace_section_tile(lib=None):
+    """mh_ace_section_tile: evaluations of one tile of the plan's scan."""
+    lib = lib or load_library()
+    lib.mh_ace_section_tile.restype = C.c_uint32
+    lib.mh_ace_section_tile.argtypes = []
+    return int(lib.mh_ace_section_tile())
+
+
+def bitwise_section(ctx, ops, log_n=None, want_results=False):
+    """mh_bitwise_section_build: the bitwise chiplet's rows on the device from the operations in program order (BITWISE_OP_DTYPE
+    records) -> (Trace [2^log_n, 13], BitwiseSectionInfo, results); log_n None: max(6, ceil log2 n_rows).  results is the uint32 result
+    per op when want_results, else None.  A defect of the list raises MidenHipError with `e.info`."""
+    o, op = _bitwise_ops(ops)
+    lib = ctx.lib
+    lib.mh_bitwise_section_build.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.c_void_p,
+                                             C.POINTER(BitwiseSectionInfo)]
+    h, info = C.c_void_p(), BitwiseSectionInfo()
+    res = np.zeros(o.size, dtype=np.uint32) if want_results else None
+    rp = res.ctypes.data_as(C.c_void_p) if want_results and o.size else None
+    rc = lib.mh_bitwise_section_build(ctx.h, op, o.size, -1 if log_n is None else int(log_n), C.byref(h), rp, C.byref(info))
+    _mem_section_result(lib, ctx, rc, info)
+    return Trace.from_handle(ctx, h, int(info.log_n), 13), info, res
+
+
+def ace_section(ctx, evals, felts, log_n=None):
+    """mh_ace_section_build: the ACE chiplet's rows on the device from the circuit evaluations in clock order (ACE_EVAL_DTYPE records
+    whose `payload` points into `felts`: 2 num_vars felts as read from memory, then num_eval instructions) -> (Trace [2^log_n, 16],
+    AceSectionInfo); log_n None: max(6, ceil log2 n_rows).  A defect of the list raises MidenHipError with `e.info`."""
+    e, ep, f, fp = _ace_evals(evals, felts)
+    lib = ctx.lib
+    lib.mh_ace_section_build.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p),
+                                         C.POINTER(AceSectionInfo)]
+    h, info = C.c_void_p(), AceSectionInfo()
+    rc = lib.mh_ace_section_build(ctx.h, ep, e.size, fp, f.size, -1 if log_n is None else int(log_n), C.byref(h), C.byref(info))
+    _mem_section_result(lib, ctx, rc, info)
+    return Trace.from_handle(ctx, h, int(info.log_n), 16), info
+
+
+def kernel_rom_section(ctx, procs, calls, log_n=None, want_digests=False):
+    """mh_kernel_rom_section_build: the kernel ROM's rows on the device from the declared procedure digests and the called digests
+    (uint64 [n][4] each) -> (Trace [2^log_n, 5], KernelRomSectionInfo, digests); log_n None: max(6, ceil log2 n_rows).  digests is the
+    uint64 [n_rows, 4] array of the rows' digests in trace order when want_digests, else None.  A defect raises MidenHipError with
+    `e.info`."""
+    p, pp = _digests(procs)
+    k, kp = _digests(calls)
+    lib = ctx.lib
+    lib.mh_kernel_rom_section_build.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p),
+                                                C.c_void_p, C.POINTER(KernelRomSectionInfo)]
+    h, info = C.c_void_p(), KernelRomSectionInfo()
+    dig = np.zeros((p.shape[0], 4), dtype=np.uint64) if want_digests else None
+    dp = dig.ctypes.data_as(C.c_void_p) if want_digests and dig.size else None
+    rc = lib.mh_kernel_rom_section_build(ctx.h, pp, p.shape[0], kp, k.shape[0], -1 if log_n is None else int(log_n), C.byref(h), dp, C.byref(info))
+    _mem_section_result(lib, ctx, rc, info)
+    return Trace.from_handle(ctx, h, int(info.log_n), 5), info, (dig[:int(info.n_rows)] if want_digests else None)
 
 
 def load_library():
@@ -1743,6 +1883,87 @@ class Miden:
         rc = lib.mh_miden_hasher_section(self.ctx.h, chiplets.h, op, o.size, fp, f.size, rp, C.byref(info))
         _mem_section_result(lib, self.ctx, rc, info)
         return info, res
+
+    def bitwise_section(self, chiplets, start_row, ops, want_results=False):
+        """mh_miden_bitwise_section: the bitwise chiplet's rows written in place into the device-resident chiplets Trace at rows
+        [start_row, start_row + 8 n_ops): columns 0, 1 = 1, 0 and columns 2..14; everything else stays -> (BitwiseSectionInfo, results
+        or None).  A defect of the list, or a section that does not fit, raises MidenHipError with `e.info`; nothing was written then."""
+        lib = self.ctx.lib
+        if not isinstance(chiplets, Trace):
+            raise MidenHipError("Miden.bitwise_section: a Trace object expected")
+        o, op = _bitwise_ops(ops)
+        lib.mh_miden_bitwise_section.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                 C.POINTER(BitwiseSectionInfo)]
+        info = BitwiseSectionInfo()
+        res = np.zeros(o.size, dtype=np.uint32) if want_results else None
+        rp = res.ctypes.data_as(C.c_void_p) if want_results and o.size else None
+        rc = lib.mh_miden_bitwise_section(self.ctx.h, chiplets.h, int(start_row), op, o.size, rp, C.byref(info))
+        _mem_section_result(lib, self.ctx, rc, info)
+        return info, res
+
+    def ace_section(self, chiplets, start_row, evals, felts):
+        """mh_miden_ace_section: the ACE chiplet's rows written in place into the device-resident chiplets Trace from start_row on:
+        columns 0..3 = 1, 1, 1, 0 and columns 4..19; everything else stays -> AceSectionInfo.  A defect of the list, or a section that
+        does not fit, raises MidenHipError with `e.info`; nothing was written then."""
+        lib = self.ctx.lib
+        if not isinstance(chiplets, Trace):
+            raise MidenHipError("Miden.ace_section: a Trace object expected")
+        e, ep, f, fp = _ace_evals(evals, felts)
+        lib.mh_miden_ace_section.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.POINTER(AceSectionInfo)]
+        info = AceSectionInfo()
+        rc = lib.mh_miden_ace_section(self.ctx.h, chiplets.h, int(start_row), ep, e.size, fp, f.size, C.byref(info))
+        _mem_section_result(lib, self.ctx, rc, info)
+        return info
+
+    def kernel_rom_section(self, chiplets, start_row, procs, calls, want_digests=False):
+        """mh_miden_kernel_rom_section: the kernel ROM's rows written in place into the device-resident chiplets Trace from start_row
+        on: columns 0..4 = 1, 1, 1, 1, 0 and columns 5..9; everything else stays -> (KernelRomSectionInfo, digests or None).  A defect,
+        or a section that does not fit, raises MidenHipError with `e.info`; nothing was written then."""
+        lib = self.ctx.lib
+        if not isinstance(chiplets, Trace):
+            raise MidenHipError("Miden.kernel_rom_section: a Trace object expected")
+        p, pp = _digests(procs)
+        k, kp = _digests(calls)
+        lib.mh_miden_kernel_rom_section.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p, C.POINTER(KernelRomSectionInfo)]
+        info = KernelRomSectionInfo()
+        dig = np.zeros((p.shape[0], 4), dtype=np.uint64) if want_digests else None
+        dp = dig.ctypes.data_as(C.c_void_p) if want_digests and dig.size else None
+        rc = lib.mh_miden_kernel_rom_section(self.ctx.h, chiplets.h, int(start_row), pp, p.shape[0], kp, k.shape[0], dp, C.byref(info))
+        _mem_section_result(lib, self.ctx, rc, info)
+        return info, (dig[:int(info.n_rows)] if want_digests else None)
+
+    def chiplets_frame(self, chiplets, padding_start):
+        """mh_miden_chiplets_frame: chip_clk = row + 1 in column 21 of every row of the device-resident chiplets Trace and, from
+        padding_start on, ones in columns 0..4 and zeros in columns 5..20; nothing else is touched."""
+        lib = self.ctx.lib
+        if not isinstance(chiplets, Trace):
+            raise MidenHipError("Miden.chiplets_frame: a Trace object expected")
+        lib.mh_miden_chiplets_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        self.ctx.check(lib.mh_miden_chiplets_frame(self.ctx.h, chiplets.h, int(padding_start)))
+
+    def chiplets_build(self, lists, log_n=None):
+        """mh_miden_chiplets_build: the finished chiplets trace on the device from the five lists of one executed program -> (Trace
+        [2^log_n, 22], ChipletsInfo); log_n None: max(6, ceil log2 trace_len).  `lists` is a mapping with the keys hash_ops, hash_felts
+        (HASH_OP_DTYPE, uint64), bitwise_ops (BITWISE_OP_DTYPE), mem_accesses (MEM_ACCESS_DTYPE), ace_evals, ace_felts (ACE_EVAL_DTYPE,
+        uint64), kernel_procs, kernel_calls (uint64 [n][4]); a missing key is an empty list.  A defect of a list, or a trace that does
+        not fit, raises MidenHipError with `e.info` naming the section; no trace exists then."""
+        lib = self.ctx.lib
+        ho, hop, hf, hfp = _hash_ops(_records(lists.get("hash_ops", ()), HASH_OP_DTYPE), lists.get("hash_felts", ()))
+        bo, bop = _bitwise_ops(lists.get("bitwise_ops", ()))
+        ma, map_ = _mem_accesses(_records(lists.get("mem_accesses", ()), MEM_ACCESS_DTYPE))
+        ae, aep, af, afp = _ace_evals(lists.get("ace_evals", ()), lists.get("ace_felts", ()))
+        kp, kpp = _digests(lists.get("kernel_procs", ()))
+        kc, kcp = _digests(lists.get("kernel_calls", ()))
+        ls = ChipletsLists(hop, ho.size, hfp, hf.size, bop, bo.size, map_, ma.size, aep, ae.size, afp, af.size, kpp, kp.shape[0], kcp, kc.shape[0])
+        lib.mh_miden_chiplets_build.argtypes = [C.c_void_p, C.POINTER(ChipletsLists), C.c_int, C.POINTER(C.c_void_p), C.POINTER(ChipletsInfo)]
+        h, info = C.c_void_p(), ChipletsInfo()
+        rc = lib.mh_miden_chiplets_build(self.ctx.h, C.byref(ls), -1 if log_n is None else int(log_n), C.byref(h), C.byref(info))
+        if rc != 0:
+            assert not h.value
+        _mem_section_result(lib, self.ctx, rc, info)
+        return Trace.from_handle(self.ctx, h, int(info.log_n), 22), info
 
     def free(self):
         if getattr(self, "h", None) and self.ctx.h:

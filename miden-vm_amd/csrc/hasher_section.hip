@@ -35,6 +35,7 @@
 #include "../../include/midenhip.h"
 #include "ctx.hpp"
 #include "gl.cuh"
+#include "hs_scan.cuh"
 #include "kernels.hpp"
 #include "poseidon2.cuh"
 #include <memory>
@@ -46,15 +47,10 @@ static_assert(sizeof(mh_hash_op) == 24, "mh_hash_op is 24 bytes");
 static_assert(sizeof(mh_hash_result) == 136, "mh_hash_result is 17 words");
 
 namespace {
-constexpr int HS_BT = 256;
-constexpr int HS_WAVES = HS_BT / 64;
-constexpr int HS_PER_LANE = 4;
-constexpr u32 HS_TILE = HS_BT * HS_PER_LANE;  // ops (plan) / permutations (ids) of a scan tile; mh_hasher_section_tile() tells the tests
 constexpr int HS_CHAIN_BT = 64;               // k_hs_chains: one wave a block, so that long chains spread over the CUs
 constexpr int HS_WIDTH = 20;
 constexpr int HS_CHIPLETS_WIDTH = 22;
 constexpr u32 HS_MAX_PERMS = 1u << 24;
-constexpr u32 HS_SAT = 1u << 25;              // permutation counts saturate here
 constexpr u32 HS_BUCKETS = 64;                // chain lengths 64.., 63, .., 1
 constexpr u32 HS_EMPTY = 0xFFFFFFFFu;
 constexpr unsigned long long HS_NONE = ~0ull;
@@ -71,8 +67,6 @@ struct HsWords {                 // what the host reads back
 struct HsPlan {
   u32 perms, mru, defect;
 };
-
-__device__ __forceinline__ u32 hs_sat(u32 x) { return x < HS_SAT ? x : HS_SAT; }  // x = a + b, a, b <= HS_SAT
 
 // what op `o` asks for, and the first defect it has in the order 1, 2, 3, 4
 __device__ __forceinline__ HsPlan hs_plan_op(const mh_hash_op& o, u64 n_felts) {
@@ -111,53 +105,6 @@ __device__ __forceinline__ HsPlan hs_plan_op(const mh_hash_op& o, u64 n_felts) {
   }
   if (o.payload > n_felts || need > n_felts - o.payload) p.defect = 4;
   return p;
-}
-
-// The block's HS_TILE items, HS_PER_LANE consecutive ones a lane, as pairs (a saturating, b plain): ea/eb[j] = carry + everything
-// left of the lane's item j; returns through ta/tb the carry + the whole tile.  All HS_BT threads call it.
-__device__ __forceinline__ void hs_tile_scan(const u32 (&a)[HS_PER_LANE], const u32 (&b)[HS_PER_LANE], u32 carry_a, u32 carry_b,
-                                             u32 (&ea)[HS_PER_LANE], u32 (&eb)[HS_PER_LANE], u32& ta, u32& tb, u32 (*s_wave)[2]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  u32 la = 0, lb = 0;
-#pragma unroll
-  for (int j = 0; j < HS_PER_LANE; j++) {
-    la = hs_sat(la + a[j]);
-    lb += b[j];
-  }
-  u32 ia = la, ib = lb;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const u32 oa = __shfl_up(ia, off), ob = __shfl_up(ib, off);
-    if (lane >= off) {
-      ia = hs_sat(ia + oa);
-      ib += ob;
-    }
-  }
-  if (lane == 63) {
-    s_wave[wave][0] = ia;
-    s_wave[wave][1] = ib;
-  }
-  u32 xa = __shfl_up(ia, 1), xb = __shfl_up(ib, 1);
-  if (lane == 0) xa = xb = 0;
-  __syncthreads();
-  u32 before_a = carry_a, before_b = carry_b;
-  ta = carry_a;
-  tb = carry_b;
-  for (int v = 0; v < HS_WAVES; v++) {
-    if (v == wave) {
-      before_a = ta;
-      before_b = tb;
-    }
-    ta = hs_sat(ta + s_wave[v][0]);
-    tb += s_wave[v][1];
-  }
-  ea[0] = hs_sat(before_a + xa);
-  eb[0] = before_b + xb;
-#pragma unroll
-  for (int j = 1; j < HS_PER_LANE; j++) {
-    ea[j] = hs_sat(ea[j - 1] + a[j - 1]);
-    eb[j] = eb[j - 1] + b[j - 1];
-  }
 }
 
 struct HsRun {

@@ -265,6 +265,18 @@ def _qmul(a, b):
 class Ace:
     def __init__(self):
         self.evals = {}   # clk -> rows
+        self.log = {}     # clk -> (ctx, ptr, clk, num_vars, num_eval, the felts read: n_read words, then num_eval instructions)
+
+    def eval_list(self):
+        """The evaluations made so far as (evals, felts): ACE_EVAL_DTYPE records in clock order whose `payload` points into the uint64
+        array `felts` (2 num_vars felts as read from memory, then num_eval instructions) -- the list mh_ace_section_build takes."""
+        from .. import ACE_EVAL_DTYPE
+        evals, felts = np.zeros(len(self.log), dtype=ACE_EVAL_DTYPE), []
+        for i, clk in enumerate(sorted(self.log)):
+            ctx, ptr, _, num_vars, num_eval, operands = self.log[clk]
+            evals[i] = (ctx, ptr, clk, num_vars, num_eval, 0, len(felts))
+            felts.extend(operands)
+        return evals, np.array(felts, dtype=np.uint64)
 
     def eval_circuit(self, memory, ctx, ptr, clk, num_vars, num_eval):
         """eval_circuit_impl: READ rows consume words (two wires each), EVAL rows one instruction element each; the last wire must
@@ -274,6 +286,7 @@ class Ace:
         num_wires = 2 * n_read + num_eval
         wires, id_next = [], num_wires - 1
         reads, evals = [], []
+        header, operands = (int(ctx), int(ptr), int(clk), int(num_vars), int(num_eval)), []
 
         def insert(v):
             nonlocal id_next
@@ -289,6 +302,7 @@ class Ace:
 
         for _ in range(n_read):
             word = memory.read_word(ctx, ptr, clk)
+            operands.extend(int(x) for x in word)
             v0, v1 = (word[0], word[1]), (word[2], word[3])
             id0 = insert(v0)
             id1 = insert(v1)
@@ -296,6 +310,7 @@ class Ace:
             ptr += 4
         for _ in range(num_eval):
             ins = memory.read(ctx, ptr, clk)
+            operands.append(int(ins))
             id_l, id_r, opc = ins & ((1 << 30) - 1), (ins >> 30) & ((1 << 30) - 1), ins >> 60
             vl, vr = read_value(id_l), read_value(id_r)
             if opc == 0:
@@ -318,6 +333,7 @@ class Ace:
         for i, (p_, eval_op, id0, v0, id1, v1, id2, v2) in enumerate(evals):
             rows[n_read + i] = [0, 1, ctx, p_, clk, eval_op, id0, v0[0], v0[1], id1, v1[0], v1[1], id2, v2[0], v2[1], next(mult)]
         self.evals[int(clk)] = rows
+        self.log[int(clk)] = header + (operands,)
         return rows
 
     def section(self):
@@ -331,9 +347,20 @@ class KernelRom:
             return b"".join(int(x).to_bytes(8, "little") for x in d)
         self.procs = {key(d): [[int(x) % P for x in d], 0] for d in proc_hashes}
         self._key = key
+        self.declared = [[int(x) for x in d] for d in proc_hashes]   # as declared, duplicates included
+        self.calls = []                                              # the digests called, in call order
 
     def access_proc(self, digest):
         self.procs[self._key(digest)][1] += 1
+        self.calls.append([int(x) for x in digest])
+
+    def proc_array(self):
+        """The declared procedure digests as uint64 [n, 4]: the `procs` of mh_kernel_rom_section_build."""
+        return np.array(self.declared, dtype=np.uint64).reshape(-1, 4)
+
+    def call_array(self):
+        """The calls made so far as uint64 [n, 4], in call order: the `calls` of mh_kernel_rom_section_build."""
+        return np.array(self.calls, dtype=np.uint64).reshape(-1, 4)
 
     def digests(self):
         """The kernel digests in trace order = the order of `aux_inputs[8..]` that balances the INIT removes."""
@@ -354,6 +381,16 @@ class Chiplets:
     def trace_len(self):
         h = -(-len(self.hasher.rows) // 8) * 8
         return h + len(self.bitwise.ops) * 8 + self.memory.num_rows + sum(len(r) for r in self.ace.evals.values()) + len(self.kernel_rom.procs) + 1
+
+    def lists(self):
+        """The five lists of what has been executed so far, as Miden.chiplets_build / mh_miden_chiplets_build takes them."""
+        from .. import BITWISE_OP_DTYPE
+        hash_ops, hash_felts = self.hasher.op_list()
+        ace_evals, ace_felts = self.ace.eval_list()
+        return dict(hash_ops=hash_ops, hash_felts=hash_felts,
+                    bitwise_ops=np.array(self.bitwise.ops, dtype=BITWISE_OP_DTYPE).reshape(-1), mem_accesses=self.memory.access_array(),
+                    ace_evals=ace_evals, ace_felts=ace_felts, kernel_procs=self.kernel_rom.proc_array(),
+                    kernel_calls=self.kernel_rom.call_array())
 
     def poseidon2_trace_len(self):
         return (len(self.hasher.perm_requests) + 1) * MA.HASH_CYCLE_LEN
