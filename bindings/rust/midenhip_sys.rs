@@ -234,6 +234,29 @@ pub struct mh_chiplets_info {
     pub kernel_rom: mh_kernel_rom_section_info,
 }
 
+/// One message of mh_keccak_traces_build: bytes[offset .. offset + len), chunk_head = the base of its chunk-tape segment in chunks (24 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_keccak_msg {
+    pub offset: u64,
+    pub len: u64,
+    pub chunk_head: u64,
+}
+
+/// mh_keccak_traces_build: the permutations, the sponge's active rows, the least heights of both traces, and the defect that refused
+/// the call (0 none, 1 offset + len past n_bytes, 2 chunk pointer beyond 32 bits, 3 more than 2^24 rows, 4 a null pointer, 5 / 6
+/// log_round / log_sponge too small; see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_keccak_traces_info {
+    pub n_perms: u64,
+    pub sponge_rows: u64,
+    pub round_rows_needed: u64,
+    pub sponge_rows_needed: u64,
+    pub defect_kind: i32,
+    pub defect_index: u64,
+}
+
 /// An encoded denominator whose net multiplicity is not zero (mh_check_balance*; the reference's `Unmatched`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -634,4 +657,10 @@ unsafe extern "C" {
     pub fn mh_miden_kernel_rom_section(ctx: *mut mh_ctx, chiplets: *mut mh_trace, start_row: u64, procs: *const u64, n_procs: usize, calls: *const u64, n_calls: usize, digests: *mut u64, info: *mut mh_kernel_rom_section_info) -> c_int;
     pub fn mh_miden_chiplets_build(ctx: *mut mh_ctx, lists: *const mh_chiplets_lists, log_n: c_int, out: *mut *mut mh_trace, info: *mut mh_chiplets_info) -> c_int;
     pub fn mh_miden_chiplets_frame(ctx: *mut mh_ctx, chiplets: *mut mh_trace, padding_start: u64) -> c_int;
+    // the precompile prover's Keccak round (width 68) and sponge (width 67) traces built on the device (csrc/keccak_traces.hip); the
+    // first two are host only; outputs, digests and info may be null
+    pub fn mh_keccak_round_program(out: *mut i32) -> c_int;
+    pub fn mh_keccak_round_levels(out: *mut i32) -> c_int;
+    pub fn mh_keccak_round_trace_build(ctx: *mut mh_ctx, states: *const u64, n_perms: usize, log_n: c_int, out: *mut *mut mh_trace, outputs: *mut u64) -> c_int;
+    pub fn mh_keccak_traces_build(ctx: *mut mh_ctx, bytes: *const u8, n_bytes: usize, msgs: *const mh_keccak_msg, n_msgs: usize, log_round: c_int, log_sponge: c_int, round_out: *mut *mut mh_trace, sponge_out: *mut *mut mh_trace, digests: *mut u8, info: *mut mh_keccak_traces_info) -> c_int;
 }

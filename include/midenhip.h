@@ -1312,6 +1312,49 @@ int mh_miden_chiplets_build(mh_ctx* ctx, const mh_chiplets_lists* lists, int log
                             mh_chiplets_info* info /* may be NULL */);
 int mh_miden_chiplets_frame(mh_ctx* ctx, mh_trace* chiplets /* width 22 */, uint64_t padding_start);
 
+/* ---- the precompile prover's Keccak round and sponge traces, built on the device from messages ----
+ * mh_keccak_traces_build takes the bytes a session hashes and returns the main traces of KeccakRoundAir (68 columns, index 2 of
+ * mh_prove_precompile_traces) and KeccakSpongeAir (67 columns, index 4), device-resident: neither crosses PCIe.
+ * mh_keccak_round_trace_build is the stand-alone form for callers that hold the permutation inputs.  Device stage:
+ * csrc/keccak_traces.hip.  The rule is the reference's (hash/keccak/round/mod.rs:725-806 generate_trace_from_states_inner,
+ * hash/keccak/sponge/trace.rs:176-262 SpongeRequires, :388-585 generate_trace) and is fixed; the 128-slot round programme
+ * (round/program.rs slots()) and the 24 round constants live in the library.
+ *   messages  message i is bytes[offset .. offset + len); chunk_head = the base of its chunk-tape segment, in chunks of four lanes
+ *             (ChunkRequires::require gives it).  Keccak-256: rate 136, pad10*1 with 0x01 / 0x80; len / 136 + 1 blocks, one
+ *             permutation and 32 sponge rows a block, in message order.
+ *   heights   round: max(2, next_pow2(ceil(max(n_perms, 1) / 2) * 3200)) -- no permutation lays one inactive cycle; sponge:
+ *             max(32, next_pow2(32 n_perms)).  log_* = -1 takes these; a larger one pads by the generators' rule (round: zero rows, ip
+ *             running on in both lanes; sponge: seq_id running on, bytes_left falling by 8 per rate slot modulo p, chunk_ptr held); a
+ *             smaller one is refused with the heights needed in `info`.
+ *   refusals  before any trace is allocated or written, MH_ERR_INVALID, *round_out / *sponge_out untouched, `info` filled:
+ *             defect_kind 1 offset + len past n_bytes; 2 4 chunk_head + the message's lanes (4 max(1, ceil(len / 32))) not below
+ *             2^32; 3 more than 2^24 rows in either trace; 4 a NULL pointer where one is required (defect_index 0); 5 / 6 log_round /
+ *             log_sponge below the height needed (defect_index = the rows needed).  defect_index = the message, for kinds 1..3 the lowest.
+ *   results   digests[i] = the 32-byte Keccak-256 digest of message i; outputs[n] = Keccak-f[1600] of states[n].  Asking for either
+ *             makes the call wait for the stream; without them the call returns with the kernels enqueued on the context's stream.
+ * The byte-pair table's three multiplicity columns are not counted here: mh_fill_multiplicities_precompile_traces does that.
+ * Every cell is written by one lane; a second call leaves the same bytes.
+ * Not in scope: the chunk / node, Poseidon2, transcript, uint and EC chiplets' traces; device-resident message bytes; sharded runs. */
+typedef struct mh_keccak_msg { uint64_t offset, len, chunk_head; } mh_keccak_msg;
+typedef struct mh_keccak_traces_info {
+  uint64_t n_perms;             /* blocks = permutations over all messages */
+  uint64_t sponge_rows;         /* 32 n_perms: the sponge's active rows */
+  uint64_t round_rows_needed;   /* the least height of the round trace */
+  uint64_t sponge_rows_needed;  /* the least height of the sponge trace */
+  int32_t defect_kind;          /* 0 none */
+  uint64_t defect_index;
+} mh_keccak_traces_info;
+/* Host only: the round programme, (op, shift, back_a, back_b, dst_mult) per slot; op 0 NOP, 1 XOR, 2 ANDNOT, 3 ROL, 4 XORROL. */
+int mh_keccak_round_program(int32_t* out /* [128 * 5] */);
+/* Host only: the level of each slot in the device schedule, -1 for a NOP slot.  Level 0 reads only the previous round's outputs, RC
+ * or the input; any other slot lies one above the highest same-round slot it reads.  10 levels of 5 5 5 5 5 5 25 25 25 1 slots. */
+int mh_keccak_round_levels(int32_t* out /* [128] */);
+int mh_keccak_round_trace_build(mh_ctx* ctx, const uint64_t* states /* [n_perms][25] */, size_t n_perms, int log_n /* -1: least */,
+                                mh_trace** out /* width 68 */, uint64_t* outputs /* [n_perms][25] or NULL */);
+int mh_keccak_traces_build(mh_ctx* ctx, const uint8_t* bytes, size_t n_bytes, const mh_keccak_msg* msgs, size_t n_msgs, int log_round,
+                           int log_sponge /* -1: least */, mh_trace** round_out /* width 68 */, mh_trace** sponge_out /* width 67 */,
+                           uint8_t* digests /* [n_msgs][32] or NULL */, mh_keccak_traces_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

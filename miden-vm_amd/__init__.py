@@ -45,6 +45,7 @@ EXPORTS = [
     "mh_hasher_section_build", "mh_miden_hasher_section", "mh_hasher_section_tile",
     "mh_bitwise_section_build", "mh_miden_bitwise_section", "mh_ace_section_build", "mh_miden_ace_section", "mh_ace_section_tile",
     "mh_kernel_rom_section_build", "mh_miden_kernel_rom_section", "mh_miden_chiplets_build", "mh_miden_chiplets_frame",
+    "mh_keccak_round_program", "mh_keccak_round_levels", "mh_keccak_round_trace_build", "mh_keccak_traces_build",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
@@ -565,6 +566,97 @@ def kernel_rom_section(ctx, procs, calls, log_n=None, want_digests=False):
     rc = lib.mh_kernel_rom_section_build(ctx.h, pp, p.shape[0], kp, k.shape[0], -1 if log_n is None else int(log_n), C.byref(h), dp, C.byref(info))
     _mem_section_result(lib, ctx, rc, info)
     return Trace.from_handle(ctx, h, int(info.log_n), 5), info, (dig[:int(info.n_rows)] if want_digests else None)
+
+
+# ---- the precompile prover's Keccak round and sponge traces (include/midenhip.h mh_keccak_round_program .. mh_keccak_traces_build) ----
+KECCAK_MSG_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8"), ("chunk_head", "<u8")])  # mh_keccak_msg
+
+
+class KeccakTracesInfo(C.Structure):
+    """mh_keccak_traces_info: n_perms blocks = permutations, sponge_rows = 32 n_perms active sponge rows, the least heights of the two
+    traces; `defect_kind` 0 none, 1 offset + len past the bytes, 2 4 chunk_head + lanes not below 2^32, 3 more than 2^24 rows, 4 a NULL
+    pointer, 5 / 6 log_round / log_sponge below the height needed (`defect_index` = the rows needed); else `defect_index` the message."""
+    _fields_ = [("n_perms", C.c_uint64), ("sponge_rows", C.c_uint64), ("round_rows_needed", C.c_uint64), ("sponge_rows_needed", C.c_uint64),
+                ("defect_kind", C.c_int32), ("defect_index", C.c_uint64)]
+
+    def __repr__(self):
+        return (f"KeccakTracesInfo(n_perms={self.n_perms}, sponge_rows={self.sponge_rows}, round_rows_needed={self.round_rows_needed}, "
+                f"sponge_rows_needed={self.sponge_rows_needed}, defect_kind={self.defect_kind}, defect_index={self.defect_index})")
+
+
+def keccak_round_program(lib=None):
+    """mh_keccak_round_program (host only): the library's round programme -> [(op, shift, back_a, back_b, dst_mult)] * 128."""
+    lib = lib or load_library()
+    out = np.zeros((128, 5), dtype=np.int32)
+    lib.mh_keccak_round_program.argtypes = [C.c_void_p]
+    if lib.mh_keccak_round_program(out.ctypes.data_as(C.c_void_p)) != 0:
+        raise MidenHipError("mh_keccak_round_program failed")
+    return [tuple(int(x) for x in row) for row in out]
+
+
+def keccak_round_levels(lib=None):
+    """mh_keccak_round_levels (host only): the level of each of the 128 slots in the device schedule, -1 for a NOP slot."""
+    lib = lib or load_library()
+    out = np.zeros(128, dtype=np.int32)
+    lib.mh_keccak_round_levels.argtypes = [C.c_void_p]
+    if lib.mh_keccak_round_levels(out.ctypes.data_as(C.c_void_p)) != 0:
+        raise MidenHipError("mh_keccak_round_levels failed")
+    return [int(x) for x in out]
+
+
+def keccak_round_trace(ctx, states, log_n=None, want_outputs=False):
+    """mh_keccak_round_trace_build: KeccakRoundAir's main trace on the device from the permutations' 25-lane inputs (uint64 [n, 25])
+    -> Trace [2^log_n, 68], or (Trace, outputs uint64 [n, 25] = Keccak-f[1600] of each state) when want_outputs.  log_n None: the
+    least, max(2, next_pow2(ceil(max(n, 1) / 2) * 3200)); a smaller one raises MidenHipError with the rows needed."""
+    s = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, 25)
+    n = s.shape[0]
+    lib = ctx.lib
+    lib.mh_keccak_round_trace_build.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
+    h = C.c_void_p()
+    outs = np.zeros((n, 25), dtype=np.uint64) if want_outputs else None
+    op = outs.ctypes.data_as(C.c_void_p) if want_outputs and n else None
+    least = max(1, (-(-max(n, 1) // 2) * 3200 - 1).bit_length())
+    ctx.check(lib.mh_keccak_round_trace_build(ctx.h, s.ctypes.data_as(C.c_void_p) if n else None, n, -1 if log_n is None else int(log_n),
+                                              C.byref(h), op))
+    t = Trace.from_handle(ctx, h, least if log_n is None else int(log_n), 68)
+    return (t, outs) if want_outputs else t
+
+
+def keccak_traces(ctx, messages, chunk_heads, log_round=None, log_sponge=None, want_digests=False):
+    """mh_keccak_traces_build: the main traces of KeccakRoundAir and KeccakSpongeAir on the device from the messages a session hashes
+    (bytes-like each) and their chunk-tape bases in chunks (ChunkRequires.require's chunk_head) -> (round Trace [2^log_round, 68],
+    sponge Trace [2^log_sponge, 67], KeccakTracesInfo[, digests uint8 [n, 32]]).  log_* None: the least heights.  A refusal raises
+    MidenHipError with `e.info`."""
+    msgs = [bytes(m) for m in messages]
+    if len(msgs) != len(chunk_heads):
+        raise MidenHipError("keccak_traces: one chunk head per message expected")
+    rec = np.zeros(len(msgs), dtype=KECCAK_MSG_DTYPE)
+    at = 0
+    for i, (m, head) in enumerate(zip(msgs, chunk_heads)):
+        rec[i] = (at, len(m), int(head))
+        at += len(m)
+    data = np.frombuffer(b"".join(msgs), dtype=np.uint8)
+    return keccak_traces_raw(ctx, data, rec, log_round, log_sponge, want_digests)
+
+
+def keccak_traces_raw(ctx, data, msgs, log_round=None, log_sponge=None, want_digests=False):
+    """keccak_traces on the ABI's own arguments: `data` uint8, `msgs` KECCAK_MSG_DTYPE records (offset, len, chunk_head) into it."""
+    data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    rec = _records(msgs, KECCAK_MSG_DTYPE)
+    lib = ctx.lib
+    lib.mh_keccak_traces_build.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(KeccakTracesInfo)]
+    hr, hs, info = C.c_void_p(), C.c_void_p(), KeccakTracesInfo()
+    dig = np.zeros((rec.size, 32), dtype=np.uint8) if want_digests else None
+    dp = dig.ctypes.data_as(C.c_void_p) if want_digests and rec.size else None
+    rc = lib.mh_keccak_traces_build(ctx.h, data.ctypes.data_as(C.c_void_p) if data.size else None, data.size,
+                                    rec.ctypes.data_as(C.c_void_p) if rec.size else None, rec.size, -1 if log_round is None else int(log_round),
+                                    -1 if log_sponge is None else int(log_sponge), C.byref(hr), C.byref(hs), dp, C.byref(info))
+    _mem_section_result(lib, ctx, rc, info)
+    lr = int(info.round_rows_needed).bit_length() - 1 if log_round is None else int(log_round)
+    ls = int(info.sponge_rows_needed).bit_length() - 1 if log_sponge is None else int(log_sponge)
+    out = (Trace.from_handle(ctx, hr, lr, 68), Trace.from_handle(ctx, hs, ls, 67), info)
+    return out + (dig,) if want_digests else out
 
 
 def load_library():
@@ -2106,6 +2198,10 @@ class Precompile:
         sa, ns = _slot_array(slots)
         call = lambda written, *out: lib.mh_fill_multiplicities_precompile_traces(self.ctx.h, self.h, tr, _ptr(root), sa, ns, written, *out)
         return _run_fill(self.ctx, call)
+
+    def keccak_traces(self, messages, chunk_heads, log_round=None, log_sponge=None, want_digests=False):
+        """keccak_traces on this object's context: the session's traces 2 (Keccak round) and 4 (Keccak sponge) from the messages."""
+        return keccak_traces(self.ctx, messages, chunk_heads, log_round, log_sponge, want_digests)
 
     def free(self):
         if getattr(self, "h", None) and self.ctx.h:
