@@ -257,6 +257,31 @@ pub struct mh_keccak_traces_info {
     pub defect_index: u64,
 }
 
+/// One absorption of mh_poseidon2_chiplet_trace_build: the capacity, the blocks it absorbs and the two multiplicities (56 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_p2c_absorption {
+    pub cap: [u64; 4],
+    pub n_blocks: u64,
+    pub in_mult: u64,
+    pub out_mult: u64,
+}
+
+/// mh_poseidon2_chiplet_plan / mh_poseidon2_chiplet_trace_build: the ledger's sizes, the least height, the height taken and the defect
+/// that refused the call (0 none, 1 a null pointer, 2 n_blocks = 0, 3 the n_blocks do not add up to n_cycles, 4 a bad reference,
+/// 5 more than 2^20 cycles, 6 log_n too small; see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_p2c_info {
+    pub n_absorptions: u64,
+    pub n_cycles: u64,
+    pub n_levels: u64,
+    pub rows_needed: u64,
+    pub log_n: i32,
+    pub defect_kind: i32,
+    pub defect_index: u64,
+}
+
 /// An encoded denominator whose net multiplicity is not zero (mh_check_balance*; the reference's `Unmatched`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -663,4 +688,6 @@ unsafe extern "C" {
     pub fn mh_keccak_round_levels(out: *mut i32) -> c_int;
     pub fn mh_keccak_round_trace_build(ctx: *mut mh_ctx, states: *const u64, n_perms: usize, log_n: c_int, out: *mut *mut mh_trace, outputs: *mut u64) -> c_int;
     pub fn mh_keccak_traces_build(ctx: *mut mh_ctx, bytes: *const u8, n_bytes: usize, msgs: *const mh_keccak_msg, n_msgs: usize, log_round: c_int, log_sponge: c_int, round_out: *mut *mut mh_trace, sponge_out: *mut *mut mh_trace, digests: *mut u8, info: *mut mh_keccak_traces_info) -> c_int;
+    pub fn mh_poseidon2_chiplet_plan(abs: *const mh_p2c_absorption, n_abs: usize, refs: *const i64, n_cycles: usize, start: *mut u64, level: *mut u32, info: *mut mh_p2c_info) -> c_int;
+    pub fn mh_poseidon2_chiplet_trace_build(ctx: *mut mh_ctx, abs: *const mh_p2c_absorption, n_abs: usize, blocks: *const u64, refs: *const i64, n_cycles: usize, log_n: c_int, out: *mut *mut mh_trace, digests: *mut u64, outputs: *mut u64, info: *mut mh_p2c_info) -> c_int;
 }

@@ -1355,6 +1355,56 @@ int mh_keccak_traces_build(mh_ctx* ctx, const uint8_t* bytes, size_t n_bytes, co
                            int log_sponge /* -1: least */, mh_trace** round_out /* width 68 */, mh_trace** sponge_out /* width 67 */,
                            uint8_t* digests /* [n_msgs][32] or NULL */, mh_keccak_traces_info* info /* may be NULL */);
 
+/* ---- the precompile prover's Poseidon2 chiplet trace, built on the device from the absorption ledger ----
+ * mh_poseidon2_chiplet_trace_build takes the ledger of Poseidon2Requires -- every absorption's capacity, block count and the two
+ * multiplicities, the rate blocks in absorption order -- and returns the main trace of Poseidon2Air (32 columns, index 1 of
+ * mh_prove_precompile_traces, mh_check_precompile_traces and mh_fill_multiplicities_precompile_traces), device-resident.  Device
+ * stage: csrc/poseidon2_chiplet.hip; the planner (mh_poseidon2_chiplet_plan, host only): csrc/poseidon2_chiplet_plan.cpp.  The rule is
+ * the reference's (transcript/poseidon2/trace.rs:217-420 generate_trace / write_cycle) and is fixed.
+ *   columns   perm_seq_id 0, in_mult 1, out_mult 2, is_absorb 3, state 4..15, witnesses 16..18, cube registers 19..31.
+ *   layout    absorption i lies on cycles start_i .. start_i + n_blocks_i - 1 (16 rows a cycle), start_i = the n_blocks before it.
+ *             perm_seq_id = the cycle on its 16 rows, padding included; every other cell of a padding cycle is 0.  in_mult and out_mult
+ *             (mod p) stand on all rows of the absorption's cycles, is_absorb = 1 on every cycle but its first.
+ *   state     cycle k of an absorption starts from (first half of block k, second half, cap) for k = 0, else the capacity is the previous
+ *             cycle's output 8..11.  The digest is the last cycle's output 0..3.  Felts and multiplicities are any uint64_t, reduced mod p.
+ *   rows      0: the input, the 12 cubes of M_E state + ARK_EXT_INITIAL[0]; 1..3: before external rounds 1..3 with their cubes; 4..10:
+ *             before three internal rounds, the three S-box outputs in the witnesses, the cubes of s0 + ARK_INT in registers 0..2; 11:
+ *             before internal round 21, its output in witness 0, the 12 cubes of the first terminal round in registers 0..11, the cube of
+ *             the internal S-box input in register 12; 12..14: terminal rounds 1..3; 15: the output, no cube.  All else 0.
+ *   refs      refs[c][h] = -1: half h of block c is the literal blocks[c][4 h .. 4 h + 3]; otherwise the index of an EARLIER absorption
+ *             whose digest is that half (the literal is not read): the node and transcript absorptions hash digests, and no permutation
+ *             runs on the host.  level = 0 without a reference, else one above the highest level referenced; the device runs level
+ *             by level.  refs = NULL: all literal.
+ *   heights   max(16, next_pow2(16 n_cycles)): no padding cycle is required.  log_n = -1 takes it; a larger one pads; a smaller one
+ *             is refused.
+ *   refusals  before anything is allocated, MH_ERR_INVALID, *out untouched, `info` filled, mh_last_error names kind and index; the
+ *             lowest kind first and within it the lowest index: defect_kind 1 a NULL pointer where one is required (index 0); 2 an
+ *             absorption with n_blocks = 0 (index: the absorption); 3 the n_blocks do not add up to n_cycles (index: the first absorption
+ *             that runs past it, n_abs when the list ends short); 4 a reference that is neither -1 nor the index of an earlier absorption
+ *             (index 2 cycle + half); 5 more than 2^20 cycles (2^24 rows; index: n_cycles); 6 log_n below the height needed (index:
+ *             the rows needed; the build entry only).
+ *   results   digests[i] = the digest of absorption i, outputs[c] = the permutation output of cycle c.  Asking for either makes the
+ *             call wait for the stream; without them it returns with the kernels enqueued on the context's stream.
+ * Every cell is written by one lane, no atomics; a second call leaves the same bytes.
+ * Not in scope: interning absorptions and counting in_mult / out_mult (the host ledger does both without hashing); the chunk / node,
+ * transcript, uint and EC chiplets' traces; device-resident inputs; sharded contexts; more than 2^24 rows. */
+typedef struct mh_p2c_absorption { uint64_t cap[4]; uint64_t n_blocks, in_mult, out_mult; } mh_p2c_absorption; /* 56 bytes */
+typedef struct mh_p2c_info {
+  uint64_t n_absorptions, n_cycles;
+  uint64_t n_levels;      /* 0 without an absorption */
+  uint64_t rows_needed;   /* the least height */
+  int32_t log_n;          /* the height taken (plan: the least) */
+  int32_t defect_kind;    /* 0 none */
+  uint64_t defect_index;
+} mh_p2c_info;
+/* Host only: validation, the start cycle and the level of every absorption. */
+int mh_poseidon2_chiplet_plan(const mh_p2c_absorption* abs, size_t n_abs, const int64_t* refs /* [n_cycles][2] or NULL */, size_t n_cycles,
+                              uint64_t* start /* [n_abs] or NULL */, uint32_t* level /* [n_abs] or NULL */, mh_p2c_info* info);
+int mh_poseidon2_chiplet_trace_build(mh_ctx* ctx, const mh_p2c_absorption* abs, size_t n_abs, const uint64_t* blocks /* [n_cycles][8] */,
+                                     const int64_t* refs /* [n_cycles][2] or NULL */, size_t n_cycles, int log_n /* -1: least */,
+                                     mh_trace** out /* width 32 */, uint64_t* digests /* [n_abs][4] or NULL */,
+                                     uint64_t* outputs /* [n_cycles][12] or NULL */, mh_p2c_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

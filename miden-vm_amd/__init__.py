@@ -46,6 +46,7 @@ EXPORTS = [
     "mh_bitwise_section_build", "mh_miden_bitwise_section", "mh_ace_section_build", "mh_miden_ace_section", "mh_ace_section_tile",
     "mh_kernel_rom_section_build", "mh_miden_kernel_rom_section", "mh_miden_chiplets_build", "mh_miden_chiplets_frame",
     "mh_keccak_round_program", "mh_keccak_round_levels", "mh_keccak_round_trace_build", "mh_keccak_traces_build",
+    "mh_poseidon2_chiplet_plan", "mh_poseidon2_chiplet_trace_build",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
@@ -657,6 +658,74 @@ def keccak_traces_raw(ctx, data, msgs, log_round=None, log_sponge=None, want_dig
     ls = int(info.sponge_rows_needed).bit_length() - 1 if log_sponge is None else int(log_sponge)
     out = (Trace.from_handle(ctx, hr, lr, 68), Trace.from_handle(ctx, hs, ls, 67), info)
     return out + (dig,) if want_digests else out
+
+
+# ---- the precompile prover's Poseidon2 chiplet trace (include/midenhip.h mh_poseidon2_chiplet_plan, mh_poseidon2_chiplet_trace_build) ----
+P2C_ABSORPTION_DTYPE = np.dtype([("cap", "<u8", (4,)), ("n_blocks", "<u8"), ("in_mult", "<u8"), ("out_mult", "<u8")])  # mh_p2c_absorption
+
+
+class Poseidon2ChipletInfo(C.Structure):
+    """mh_p2c_info: the ledger's absorptions, cycles and levels, the least height and the height taken; `defect_kind` 0 none, 1 a NULL
+    pointer, 2 n_blocks = 0 (`defect_index` the absorption), 3 the n_blocks do not add up to n_cycles (the first absorption that runs
+    past, n_abs when the list ends short), 4 a bad reference (2 cycle + half), 5 more than 2^20 cycles, 6 log_n below the height needed
+    (the rows needed)."""
+    _fields_ = [("n_absorptions", C.c_uint64), ("n_cycles", C.c_uint64), ("n_levels", C.c_uint64), ("rows_needed", C.c_uint64),
+                ("log_n", C.c_int32), ("defect_kind", C.c_int32), ("defect_index", C.c_uint64)]
+
+    def __repr__(self):
+        return (f"Poseidon2ChipletInfo(n_absorptions={self.n_absorptions}, n_cycles={self.n_cycles}, n_levels={self.n_levels}, "
+                f"rows_needed={self.rows_needed}, log_n={self.log_n}, defect_kind={self.defect_kind}, defect_index={self.defect_index})")
+
+
+def _p2c_args(absorptions, blocks, refs):
+    a = _records(absorptions, P2C_ABSORPTION_DTYPE)
+    b = np.ascontiguousarray(blocks, dtype=np.uint64).reshape(-1, 8)
+    r = None if refs is None else np.ascontiguousarray(refs, dtype=np.int64).reshape(-1, 2)
+    if r is not None and r.shape[0] != b.shape[0]:
+        raise MidenHipError("poseidon2_chiplet: one pair of references per block expected")
+    return a, b, r
+
+
+def poseidon2_chiplet_plan(absorptions, n_cycles, refs=None, lib=None):
+    """mh_poseidon2_chiplet_plan (host only): validates the ledger -> (start uint64 [n_abs], level uint32 [n_abs], Poseidon2ChipletInfo).
+    `absorptions`: P2C_ABSORPTION_DTYPE records, `refs` int64 [n_cycles, 2] or None.  A defect raises MidenHipError with `e.info`."""
+    lib = lib or load_library()
+    a = _records(absorptions, P2C_ABSORPTION_DTYPE)
+    r = None if refs is None else np.ascontiguousarray(refs, dtype=np.int64).reshape(-1, 2)
+    if r is not None and r.shape[0] != int(n_cycles):
+        raise MidenHipError("poseidon2_chiplet_plan: one pair of references per cycle expected")
+    start, level, info = np.zeros(a.size, dtype=np.uint64), np.zeros(a.size, dtype=np.uint32), Poseidon2ChipletInfo()
+    lib.mh_poseidon2_chiplet_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(Poseidon2ChipletInfo)]
+    rc = lib.mh_poseidon2_chiplet_plan(a.ctypes.data_as(C.c_void_p) if a.size else None, a.size, r.ctypes.data_as(C.c_void_p) if r is not None and r.size else None,
+                                       int(n_cycles), start.ctypes.data_as(C.c_void_p) if a.size else None,
+                                       level.ctypes.data_as(C.c_void_p) if a.size else None, C.byref(info))
+    if rc != 0:
+        e = MidenHipError(f"mh_poseidon2_chiplet_plan: defect {info.defect_kind}, index {info.defect_index}")
+        e.info = info
+        raise e
+    return start, level, info
+
+
+def poseidon2_chiplet_trace(ctx, absorptions, blocks, refs=None, log_n=None, want_digests=False, want_outputs=False):
+    """mh_poseidon2_chiplet_trace_build: Poseidon2Air's main trace on the device from the absorption ledger -- `absorptions`
+    P2C_ABSORPTION_DTYPE records (cap, n_blocks, in_mult, out_mult), `blocks` uint64 [n_cycles, 8] in absorption order, `refs` int64
+    [n_cycles, 2] (-1: the literal half; else the earlier absorption whose digest is that half) or None -> (Trace [2^log_n, 32],
+    Poseidon2ChipletInfo[, digests uint64 [n_abs, 4]][, outputs uint64 [n_cycles, 12]]).  log_n None: the least height,
+    max(16, next_pow2(16 n_cycles)).  A refusal raises MidenHipError with `e.info`."""
+    a, b, r = _p2c_args(absorptions, blocks, refs)
+    lib = ctx.lib
+    lib.mh_poseidon2_chiplet_trace_build.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p),
+                                                     C.c_void_p, C.c_void_p, C.POINTER(Poseidon2ChipletInfo)]
+    h, info = C.c_void_p(), Poseidon2ChipletInfo()
+    dig = np.zeros((a.size, 4), dtype=np.uint64) if want_digests else None
+    outs = np.zeros((b.shape[0], 12), dtype=np.uint64) if want_outputs else None
+    rc = lib.mh_poseidon2_chiplet_trace_build(ctx.h, a.ctypes.data_as(C.c_void_p) if a.size else None, a.size, b.ctypes.data_as(C.c_void_p) if b.size else None,
+                                              r.ctypes.data_as(C.c_void_p) if r is not None and r.size else None, b.shape[0],
+                                              -1 if log_n is None else int(log_n), C.byref(h), dig.ctypes.data_as(C.c_void_p) if want_digests and a.size else None,
+                                              outs.ctypes.data_as(C.c_void_p) if want_outputs and b.size else None, C.byref(info))
+    _mem_section_result(lib, ctx, rc, info)
+    out = (Trace.from_handle(ctx, h, int(info.log_n), 32), info)
+    return out + ((dig,) if want_digests else ()) + ((outs,) if want_outputs else ())
 
 
 def load_library():
@@ -2198,6 +2267,10 @@ class Precompile:
         sa, ns = _slot_array(slots)
         call = lambda written, *out: lib.mh_fill_multiplicities_precompile_traces(self.ctx.h, self.h, tr, _ptr(root), sa, ns, written, *out)
         return _run_fill(self.ctx, call)
+
+    def poseidon2_trace(self, absorptions, blocks, refs=None, log_n=None, want_digests=False, want_outputs=False):
+        """poseidon2_chiplet_trace on this object's context: the session's trace 1 (Poseidon2) from the absorption ledger."""
+        return poseidon2_chiplet_trace(self.ctx, absorptions, blocks, refs, log_n, want_digests, want_outputs)
 
     def keccak_traces(self, messages, chunk_heads, log_round=None, log_sponge=None, want_digests=False):
         """keccak_traces on this object's context: the session's traces 2 (Keccak round) and 4 (Keccak sponge) from the messages."""

@@ -207,6 +207,27 @@ class Poseidon2Requires:
             self._digests[idx] = out[0:4]
         return self._digests[idx]
 
+    def lists(self, refs=False):
+        """The ledger as mh_poseidon2_chiplet_trace_build takes it -> (absorptions [(cap[4], n_blocks, in_mult, out_mult)], blocks uint64
+        [cycles, 8], refs int64 [cycles, 2]).  refs=False: every half is its literal (-1).  refs=True: a half that equals the digest of an
+        earlier absorption becomes that absorption's index (the lowest such), and its literal is overwritten with a poison value."""
+        absorptions = [(tuple(cap), len(blocks), im, om) for cap, blocks, _, im, om in self.absorptions]
+        lit = np.array([list(r0) + list(r1) for _, blocks, _, _, _ in self.absorptions for r0, r1 in blocks], dtype=np.uint64).reshape(-1, 8)
+        ref = np.full((lit.shape[0], 2), -1, dtype=np.int64)
+        if refs:
+            seen = {}
+            for idx, (_, blocks, start, _, _) in enumerate(self.absorptions):
+                for k, halves in enumerate(blocks):
+                    for h, half in enumerate(halves):
+                        src = seen.get(tuple(half))
+                        if src is not None:
+                            ref[start + k, h] = src
+                            lit[start + k, 4 * h:4 * h + 4] = self.POISON
+                seen.setdefault(tuple(int(x) for x in self.digest(idx)), idx)
+        return absorptions, lit, ref
+
+    POISON = 0xDEAD0000BEEF0001
+
 
 def poseidon2_chiplet_trace(requires, min_height=0, permute_batch=None):
     """`generate_trace` / `write_cycle` (transcript/poseidon2/trace.rs:217-420): the cycles of every absorption in the order they were
