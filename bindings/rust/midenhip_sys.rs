@@ -282,6 +282,65 @@ pub struct mh_p2c_info {
     pub defect_index: u64,
 }
 
+/// One stored value of mh_uint_traces_build: pointer, bound pointer, eight 32-bit limbs (least first) and the reads of the row from
+/// outside the two chiplets (48 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_uint_row {
+    pub ptr: u32,
+    pub bound_ptr: u32,
+    pub value: [u32; 8],
+    pub val_reads: u32,
+    pub limb_reads: u32,
+}
+
+/// kappa_a a b +- kappa_c c = r (mod bound + 1) over store pointers (40 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_uint_mul_op {
+    pub a: u32,
+    pub b: u32,
+    pub c: u32,
+    pub r: u32,
+    pub bound: u32,
+    pub kappa_a: u32,
+    pub kappa_c: u32,
+    pub is_sub: u32,
+    pub mult: u64,
+}
+
+/// a + b = c (mod bound + 1) over store pointers; pointer 0 in b or c: absent (32 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_uint_add_op {
+    pub a: u32,
+    pub b: u32,
+    pub c: u32,
+    pub bound: u32,
+    pub nz: u32,
+    pub reserved: u32,
+    pub mult: u64,
+}
+
+/// mh_uint_traces_plan / mh_uint_traces_build: the lists' sizes, the least heights and the ones taken, and the defect that refused the
+/// call: section 0 store, 1 multiply, 2 add; kind 0 none, 1..7 the planner's, 8..14 the device's witness pass (see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_uint_traces_info {
+    pub n_store: u64,
+    pub n_mul: u64,
+    pub n_add: u64,
+    pub usm_rows_needed: u64,
+    pub usm_rows: u64,
+    pub add_rows_needed: u64,
+    pub add_rows: u64,
+    pub defect_section: i32,
+    pub defect_kind: i32,
+    pub defect_index: u64,
+    pub defect_operand: i32,
+    pub reserved: i32,
+}
+
 /// An encoded denominator whose net multiplicity is not zero (mh_check_balance*; the reference's `Unmatched`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -690,4 +749,6 @@ unsafe extern "C" {
     pub fn mh_keccak_traces_build(ctx: *mut mh_ctx, bytes: *const u8, n_bytes: usize, msgs: *const mh_keccak_msg, n_msgs: usize, log_round: c_int, log_sponge: c_int, round_out: *mut *mut mh_trace, sponge_out: *mut *mut mh_trace, digests: *mut u8, info: *mut mh_keccak_traces_info) -> c_int;
     pub fn mh_poseidon2_chiplet_plan(abs: *const mh_p2c_absorption, n_abs: usize, refs: *const i64, n_cycles: usize, start: *mut u64, level: *mut u32, info: *mut mh_p2c_info) -> c_int;
     pub fn mh_poseidon2_chiplet_trace_build(ctx: *mut mh_ctx, abs: *const mh_p2c_absorption, n_abs: usize, blocks: *const u64, refs: *const i64, n_cycles: usize, log_n: c_int, out: *mut *mut mh_trace, digests: *mut u64, outputs: *mut u64, info: *mut mh_p2c_info) -> c_int;
+    pub fn mh_uint_traces_plan(rows: *const mh_uint_row, n_store: usize, muls: *const mh_uint_mul_op, n_mul: usize, adds: *const mh_uint_add_op, n_add: usize, log_usm: c_int, log_add: c_int, bound_index: *mut u32, info: *mut mh_uint_traces_info) -> c_int;
+    pub fn mh_uint_traces_build(ctx: *mut mh_ctx, rows: *const mh_uint_row, n_store: usize, muls: *const mh_uint_mul_op, n_mul: usize, adds: *const mh_uint_add_op, n_add: usize, log_usm: c_int, log_add: c_int, usm_out: *mut *mut mh_trace, add_out: *mut *mut mh_trace, info: *mut mh_uint_traces_info) -> c_int;
 }

@@ -1405,6 +1405,74 @@ int mh_poseidon2_chiplet_trace_build(mh_ctx* ctx, const mh_p2c_absorption* abs, 
                                      mh_trace** out /* width 32 */, uint64_t* digests /* [n_abs][4] or NULL */,
                                      uint64_t* outputs /* [n_cycles][12] or NULL */, mh_p2c_info* info /* may be NULL */);
 
+/* ---- the precompile prover's UintStoreMul and UintAdd traces, built on the device from the ledgers ----
+ * mh_uint_traces_build takes the uint store (values at pointers, each under a bound row), the multiply-accumulate relations
+ * kappa_a a b +- kappa_c c = r (mod bound + 1) and the additions a + b = c (mod bound + 1), all over store pointers, and returns the main
+ * traces of UintStoreMulAir (44 columns, index 6) and UintAddAir (30 columns, index 7 of mh_prove_precompile_traces,
+ * mh_check_precompile_traces and mh_fill_multiplicities_precompile_traces), device-resident.  Device stage: csrc/uint_traces.hip; the
+ * planner (mh_uint_traces_plan, host only): csrc/uint_traces_plan.cpp.  The rule is the reference's (uint/trace.rs:273-386,
+ * uint/mul/trace.rs:90-180 and 278-384, uint/store_mul/trace.rs:43-72, uint/add/trace.rs:104-215) and is fixed.
+ *   rows      mh_uint_row: ptr, bound_ptr, the value in eight 32-bit limbs (least first), and the reads of the row from OUTSIDE these two
+ *             chiplets (val_reads over UintVal, limb_reads over UintLimbs: the verifier's boundary reads, the MSM and eval chiplets).
+ *             In strictly ascending ptr order -- the order of the trace; a bound row is its own bound_ptr.
+ *   store     columns 0..17, four rows per stored value: 0 the low eight 16-bit limbs of the value; 1 the high eight, the UintVal
+ *             multiplicity in cell 8 and the UintLimbs multiplicity in cell 9; 2 the sixteen 16-bit limbs of bound - value; 3 the bound's
+ *             32-bit limbs 0..3 in cells 0..3 and 4..7 in cells 8..11, the carries of value + (bound - value) out of 32-bit limbs 0..3 in
+ *             cells 4..7 and 4..6 in cells 12..14, the gap next_ptr - ptr - 1 in cell 15; ptr 16, bound_ptr 17 on all four.
+ *             UintVal multiplicity = val_reads + the c, r of every multiply relation + the a, b, c, bound of every addition + one per
+ *             row whose bound_ptr this is (+ 1 on a padding block); UintLimbs = limb_reads + the a, b, bound of every multiply
+ *             relation; both mod p.  Padding blocks: ptr = last ptr + 1 + k, its own bound, value 0.
+ *   multiply  columns 18..43, eight rows per relation (a, b, bound, quotient, r, carries, carries, c): sixteen 16-bit limbs of a, b and
+ *             the bound; the 17 16-bit limbs of q = (kappa_a a b +- kappa_c c) div (bound + 1) (0 on a subtractive underflow, where
+ *             `borrow` <= 2 moduli are added back); the 32-bit limbs of r and c; the 31 carries of the synthetic division of the
+ *             identity's coefficient polynomial by X - 2^16, each + 2^31 and split in two 16-bit halves over the 62 free cells; on the c
+ *             row mult mod p, c_ptr, kappa_c, is_sub, +-kappa_c in cells 8..12; a_ptr, b_ptr, r_ptr, bound_ptr, kappa_a, 1, borrow in
+ *             columns 37..43 on all eight.  All-zero blocks after the relations.
+ *   adder     two rows per relation: a | b limbs, carries gamma_0..3 (carry of a + b minus carry of c + k (bound + 1), mod p), b
+ *             absent, w, w S (nz: w = 1 / S, S the sum of b's limbs), b present; c | bound limbs, gamma_4..6, 0, k, c present, mult mod p,
+ *             c absent; a_ptr, b_ptr, c_ptr, bound_ptr, 1, nz in columns 24..29 on both.  Pointer 0 in b or c: absent, value 0.
+ *   heights   multiplier half next_pow2(8 max(1, n_mul)); store 4 max(1, next_pow2(n_store), multiplier rows / 4): the 44-column
+ *             trace has the store's height.  Adder next_pow2(2 max(1, n_add)).  log_usm / log_add = -1 takes them; a larger one pads
+ *             (store: padding blocks; multiplier, adder: zero blocks); a smaller one is refused.
+ *   refusals  MH_ERR_INVALID, the out pointers untouched, no trace allocated, `info` filled, mh_last_error names section (0 store, 1
+ *             multiply, 2 add), kind, index and operand; the lowest kind first, within it the multiply section before the add section
+ *             and the lowest index.  Found by the planner: 1 a NULL pointer where a count is nonzero; 2 more than 2^24 rows in either
+ *             trace, or padding pointers reaching 2^32; 3 log_usm / log_add below the height needed (index: the rows needed); 4 a store
+ *             ptr that is 0 or not above the one before; 5 a gap to the next ptr >= 2^16 (index: the row before the gap); 6 a bound_ptr
+ *             that is not stored; 7 a value above its bound's.  Found by the device's witness pass, through one packed 64-bit minimum
+ *             read back once before any trace cell is written: 8 a relation's pointer that is not stored (operand: multiply a 0, b 1,
+ *             c 2, r 3, bound 4; add a 0, b 1, c 2, bound 3; 0 is allowed for an addition's b and c only); 9 a kappa >= 2^16 (operand 0
+ *             kappa_a, 1 kappa_c); 10 r is not the canonical remainder, or the exact-division self-check of the carry chain failed; for
+ *             an addition a + b != c + k (bound + 1) for both k in {0, 1}; 11 a quotient >= 2^272; 12 a subtractive underflow beyond two
+ *             moduli; 13 a carry outside the +-2^31 window; 14 nz with b = 0.
+ *             Kind 10 for an addition is STRICTER than the reference's generator on purpose: that one asks only (a + b) mod (bound + 1)
+ *             = c, accepts 25 + 30 = 0 (mod 11) when the operands live under a foreign, larger bound, and lays a block no k in {0, 1}
+ *             satisfies.
+ * Every cell of both traces is written by the call; a second call leaves the same bytes.  The byte-pair table's Range16 column is not
+ * counted here: mh_fill_multiplicities* does that from the lookup programs.
+ * Not in scope: interning and deduplicating values and relations, and computing r (sequential, the host ledger's); sorting the store;
+ * the EC point store, group add, MSM and transcript-eval traces; device-resident inputs; sharded contexts; more than 2^24 rows. */
+typedef struct mh_uint_row { uint32_t ptr, bound_ptr; uint32_t value[8]; uint32_t val_reads, limb_reads; } mh_uint_row;          /* 48 bytes */
+typedef struct mh_uint_mul_op { uint32_t a, b, c, r, bound, kappa_a, kappa_c, is_sub; uint64_t mult; } mh_uint_mul_op;           /* 40 bytes */
+typedef struct mh_uint_add_op { uint32_t a, b, c, bound, nz, reserved; uint64_t mult; } mh_uint_add_op;                          /* 32 bytes */
+typedef struct mh_uint_traces_info {
+  uint64_t n_store, n_mul, n_add;
+  uint64_t usm_rows_needed, usm_rows;   /* the least height of the 44-column trace, and the one taken */
+  uint64_t add_rows_needed, add_rows;
+  int32_t defect_section;               /* 0 store, 1 multiply, 2 add */
+  int32_t defect_kind;                  /* 0 none */
+  uint64_t defect_index;
+  int32_t defect_operand;
+  int32_t reserved;
+} mh_uint_traces_info;
+/* Host only: kinds 1..7, the heights, and for every store row the index of its bound's row. */
+int mh_uint_traces_plan(const mh_uint_row* rows, size_t n_store, const mh_uint_mul_op* muls, size_t n_mul, const mh_uint_add_op* adds,
+                        size_t n_add, int log_usm, int log_add /* -1: least */, uint32_t* bound_index /* [n_store] or NULL */,
+                        mh_uint_traces_info* info);
+int mh_uint_traces_build(mh_ctx* ctx, const mh_uint_row* rows, size_t n_store, const mh_uint_mul_op* muls, size_t n_mul,
+                         const mh_uint_add_op* adds, size_t n_add, int log_usm, int log_add /* -1: least */,
+                         mh_trace** usm_out /* width 44 */, mh_trace** add_out /* width 30 */, mh_uint_traces_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,7 +46,7 @@ EXPORTS = [
     "mh_bitwise_section_build", "mh_miden_bitwise_section", "mh_ace_section_build", "mh_miden_ace_section", "mh_ace_section_tile",
     "mh_kernel_rom_section_build", "mh_miden_kernel_rom_section", "mh_miden_chiplets_build", "mh_miden_chiplets_frame",
     "mh_keccak_round_program", "mh_keccak_round_levels", "mh_keccak_round_trace_build", "mh_keccak_traces_build",
-    "mh_poseidon2_chiplet_plan", "mh_poseidon2_chiplet_trace_build",
+    "mh_poseidon2_chiplet_plan", "mh_poseidon2_chiplet_trace_build", "mh_uint_traces_plan", "mh_uint_traces_build",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
@@ -726,6 +726,75 @@ def poseidon2_chiplet_trace(ctx, absorptions, blocks, refs=None, log_n=None, wan
     _mem_section_result(lib, ctx, rc, info)
     out = (Trace.from_handle(ctx, h, int(info.log_n), 32), info)
     return out + ((dig,) if want_digests else ()) + ((outs,) if want_outputs else ())
+
+
+# ---- the precompile prover's UintStoreMul and UintAdd traces (include/midenhip.h mh_uint_traces_plan, mh_uint_traces_build) ----
+UINT_ROW_DTYPE = np.dtype([("ptr", "<u4"), ("bound_ptr", "<u4"), ("value", "<u4", (8,)), ("val_reads", "<u4"), ("limb_reads", "<u4")])  # mh_uint_row
+UINT_MUL_OP_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("r", "<u4"), ("bound", "<u4"), ("kappa_a", "<u4"), ("kappa_c", "<u4"),
+                              ("is_sub", "<u4"), ("mult", "<u8")])                                                                     # mh_uint_mul_op
+UINT_ADD_OP_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("bound", "<u4"), ("nz", "<u4"), ("reserved", "<u4"), ("mult", "<u8")])  # mh_uint_add_op
+
+
+class UintTracesInfo(C.Structure):
+    """mh_uint_traces_info: the lists' sizes, the least heights of the two traces and the ones taken; `defect_section` 0 store, 1 multiply,
+    2 add; `defect_kind` 0 none, 1..7 the planner's (a NULL pointer; too many rows or padding pointers past 2^32; log below the height,
+    index the rows needed; ptr 0 or not ascending; a gap >= 2^16; bound_ptr not stored; value above its bound), 8..14 the device's (a
+    pointer not stored, operand named; kappa >= 2^16; r not the canonical remainder / the addition holds for no k; quotient >= 2^272;
+    underflow beyond two moduli; a carry outside its window; nz with b = 0)."""
+    _fields_ = [("n_store", C.c_uint64), ("n_mul", C.c_uint64), ("n_add", C.c_uint64), ("usm_rows_needed", C.c_uint64), ("usm_rows", C.c_uint64),
+                ("add_rows_needed", C.c_uint64), ("add_rows", C.c_uint64), ("defect_section", C.c_int32), ("defect_kind", C.c_int32),
+                ("defect_index", C.c_uint64), ("defect_operand", C.c_int32), ("reserved", C.c_int32)]
+
+    def __repr__(self):
+        return (f"UintTracesInfo(n_store={self.n_store}, n_mul={self.n_mul}, n_add={self.n_add}, usm_rows_needed={self.usm_rows_needed}, "
+                f"usm_rows={self.usm_rows}, add_rows_needed={self.add_rows_needed}, add_rows={self.add_rows}, defect_section={self.defect_section}, "
+                f"defect_kind={self.defect_kind}, defect_index={self.defect_index}, defect_operand={self.defect_operand})")
+
+
+def _uint_lists(rows, muls, adds, sort=True):
+    """the three record arrays, the store sorted by ptr (the order of the trace; the device does not sort)"""
+    r, m, a = _records(rows, UINT_ROW_DTYPE), _records(muls, UINT_MUL_OP_DTYPE), _records(adds, UINT_ADD_OP_DTYPE)
+    if sort and r.size > 1 and not (r["ptr"][1:] >= r["ptr"][:-1]).all():
+        r = np.ascontiguousarray(r[np.argsort(r["ptr"], kind="stable")])
+    return r, m, a
+
+
+def _void_p(x):
+    return x.ctypes.data_as(C.c_void_p) if x.size else None
+
+
+def uint_traces_plan(rows, muls, adds, log_usm=None, log_add=None, lib=None, sort=True):
+    """mh_uint_traces_plan (host only): validates the store and gives the heights -> (bound_index uint32 [n_store], UintTracesInfo).
+    `rows` UINT_ROW_DTYPE, `muls` UINT_MUL_OP_DTYPE, `adds` UINT_ADD_OP_DTYPE records.  A defect raises MidenHipError with `e.info`."""
+    lib = lib or load_library()
+    r, m, a = _uint_lists(rows, muls, adds, sort)
+    bound_index, info = np.zeros(r.size, dtype=np.uint32), UintTracesInfo()
+    lib.mh_uint_traces_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                        C.POINTER(UintTracesInfo)]
+    rc = lib.mh_uint_traces_plan(_void_p(r), r.size, _void_p(m), m.size, _void_p(a), a.size, -1 if log_usm is None else int(log_usm),
+                                 -1 if log_add is None else int(log_add), _void_p(bound_index), C.byref(info))
+    if rc != 0:
+        e = MidenHipError(f"mh_uint_traces_plan: section {info.defect_section}, defect {info.defect_kind}, index {info.defect_index}")
+        e.info = info
+        raise e
+    return bound_index, info
+
+
+def uint_traces(ctx, rows, muls, adds, log_usm=None, log_add=None, sort=True):
+    """mh_uint_traces_build: UintStoreMulAir's and UintAddAir's main traces on the device from the ledgers -- `rows` UINT_ROW_DTYPE records
+    (ptr, bound_ptr, value in eight 32-bit limbs, the reads from outside the two chiplets; sorted by ptr here), `muls` UINT_MUL_OP_DTYPE
+    (kappa_a a b +- kappa_c c = r mod bound + 1 over pointers, mult), `adds` UINT_ADD_OP_DTYPE (a + b = c mod bound + 1, pointer 0 in b / c:
+    absent) -> (Trace [usm_rows, 44], Trace [add_rows, 30], UintTracesInfo).  log_* None: the least heights.  sort=False hands the store
+    over as it is.  A refusal raises MidenHipError with `e.info` (section, kind, index, operand)."""
+    r, m, a = _uint_lists(rows, muls, adds, sort)
+    lib = ctx.lib
+    lib.mh_uint_traces_build.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(UintTracesInfo)]
+    hu, ha, info = C.c_void_p(), C.c_void_p(), UintTracesInfo()
+    rc = lib.mh_uint_traces_build(ctx.h, _void_p(r), r.size, _void_p(m), m.size, _void_p(a), a.size, -1 if log_usm is None else int(log_usm),
+                                  -1 if log_add is None else int(log_add), C.byref(hu), C.byref(ha), C.byref(info))
+    _mem_section_result(lib, ctx, rc, info)
+    return (Trace.from_handle(ctx, hu, int(info.usm_rows).bit_length() - 1, 44), Trace.from_handle(ctx, ha, int(info.add_rows).bit_length() - 1, 30), info)
 
 
 def load_library():
@@ -2271,6 +2340,10 @@ class Precompile:
     def poseidon2_trace(self, absorptions, blocks, refs=None, log_n=None, want_digests=False, want_outputs=False):
         """poseidon2_chiplet_trace on this object's context: the session's trace 1 (Poseidon2) from the absorption ledger."""
         return poseidon2_chiplet_trace(self.ctx, absorptions, blocks, refs, log_n, want_digests, want_outputs)
+
+    def uint_traces(self, rows, muls, adds, log_usm=None, log_add=None):
+        """uint_traces on this object's context: the session's traces 6 (UintStoreMul) and 7 (UintAdd) from the uint ledgers."""
+        return uint_traces(self.ctx, rows, muls, adds, log_usm, log_add)
 
     def keccak_traces(self, messages, chunk_heads, log_round=None, log_sponge=None, want_digests=False):
         """keccak_traces on this object's context: the session's traces 2 (Keccak round) and 4 (Keccak sponge) from the messages."""

@@ -1236,6 +1236,33 @@ def uint_store_mul_trace(store, muls, bpl, min_height=0):
     return out
 
 
+def uint_lists(store, adds=None, muls=None, own_reads_recorded=False):
+    """The ledgers as mh_uint_traces_build takes them -> (rows, muls, adds) record arrays (UINT_ROW_DTYPE in pointer order,
+    UINT_MUL_OP_DTYPE, UINT_ADD_OP_DTYPE).  A row's val_reads / limb_reads are the reads from OUTSIDE the two chiplets: `store.reads` /
+    `store.limb_reads` as they stand, or -- own_reads_recorded=True, after `uint_add_trace` / `uint_store_mul_trace` have recorded theirs
+    -- less the reads the two op lists imply (the device adds those back, and the self-demand)."""
+    from .. import UINT_ROW_DTYPE, UINT_MUL_OP_DTYPE, UINT_ADD_OP_DTYPE
+    mul_ops, add_ops = (muls.ops if muls is not None else []), (adds.ops if adds is not None else [])
+    own_val, own_limb = {}, {}
+    if own_reads_recorded:
+        for (_ka, _kc, a, b, c, r, bound, _sub), _ in mul_ops:
+            for ptr in (a, b, bound):
+                own_limb[ptr] = own_limb.get(ptr, 0) + 1
+            for ptr in (c, r):
+                own_val[ptr] = own_val.get(ptr, 0) + 1
+        for (a, b, c, bound, _nz), _ in add_ops:
+            for ptr in (a, b, c, bound):
+                if ptr is not None:
+                    own_val[ptr] = own_val.get(ptr, 0) + 1
+    word = lambda mult: int(mult) if int(mult) < 1 << 64 else int(mult) % P                                   # noqa: E731
+    rows = np.array([(ptr, store.rows[ptr][1], tuple(_limbs(store.rows[ptr][0], 32, 8)), store.reads.get(ptr, 0) - own_val.get(ptr, 0),
+                      store.limb_reads.get(ptr, 0) - own_limb.get(ptr, 0)) for ptr in sorted(store.rows)], dtype=UINT_ROW_DTYPE).reshape(-1)
+    mul_rec = np.array([(a, b, c, r, bound, ka, kc, int(sub), word(mult)) for (ka, kc, a, b, c, r, bound, sub), mult in mul_ops],
+                       dtype=UINT_MUL_OP_DTYPE).reshape(-1)
+    add_rec = np.array([(a, b or 0, c or 0, bound, int(nz), 0, word(mult)) for (a, b, c, bound, nz), mult in add_ops], dtype=UINT_ADD_OP_DTYPE).reshape(-1)
+    return rows, mul_rec, add_rec
+
+
 class EcMsmRequires:
     """`EcMsmRequires` (ec/msm/trace.rs:146-388) + the recording layer `intro` / `combine` / `neg` / `merge_terms` (ec/msm/require.rs):
     expressions in allocation order, deduplicated by (rule, operands); every operand use adds to the operand's `mult`, every resolve (the

@@ -1,0 +1,233 @@
+"""CPU-only parts of the device-built UintStoreMul and UintAdd traces (include/midenhip.h mh_uint_traces_plan, mh_uint_traces_build): the
+planner's heights and bound indices against a restatement written here, every planner refusal by section, kind and index -- alone and
+with a higher kind behind it --, the empty lists, `uint_lists` of two sessions' ledgers against the reads the generators recorded, and
+the ABI across header, Rust declarations, Python layer and the built library."""
+import ctypes as C
+import os, re
+import numpy as np
+import pytest
+from __graft_entry__ import load_package, ROOT
+
+pkg = load_package()
+from miden_vm_amd import precompile_airs as PA  # noqa: E402
+from miden_vm_amd.testing import precompile_trace as PT  # noqa: E402
+
+FUNCS = ["mh_uint_traces_plan", "mh_uint_traces_build"]
+
+
+def library():
+    if not os.path.exists(pkg.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return pkg.load_library()
+
+
+def rows_of(entries):
+    """[(ptr, bound_ptr, value)] -> UINT_ROW_DTYPE records, in the order given"""
+    return np.array([(p, b, tuple(PT._limbs(v, 32, 8)), 0, 0) for p, b, v in entries], dtype=pkg.UINT_ROW_DTYPE).reshape(-1)
+
+
+def ops(n_mul, n_add):
+    return np.zeros(n_mul, dtype=pkg.UINT_MUL_OP_DTYPE), np.zeros(n_add, dtype=pkg.UINT_ADD_OP_DTYPE)
+
+
+def pow2(v):
+    return 1 << (max(1, v) - 1).bit_length()
+
+
+def restated_heights(n_store, n_mul, n_add):
+    mul_rows = pow2(8 * max(1, n_mul))
+    return 4 * max(1, pow2(n_store), mul_rows // 4), pow2(2 * max(1, n_add))
+
+
+GOOD = [(1, 1, 1000), (2, 2, (1 << 256) - 1), (7, 1, 1000), (8, 1, 0), (60000, 2, 1 << 255), (60001, 2, (1 << 256) - 1), (125000, 1, 999)]
+
+
+def test_planner_gives_the_restated_heights_and_bound_indices():
+    lib = library()
+    rng = np.random.default_rng(11)
+    for trial in range(40):
+        n_store, n_mul, n_add = (int(x) for x in rng.integers(0, 70, 3))
+        entries = [(1, 1, 500)] + [(2 + 3 * i, 1, int(rng.integers(0, 501))) for i in range(n_store - 1)] if n_store else []
+        m, a = ops(n_mul, n_add)
+        bound_index, info = pkg.uint_traces_plan(rows_of(entries), m, a, lib=lib)
+        usm, add = restated_heights(n_store, n_mul, n_add)
+        assert (info.n_store, info.n_mul, info.n_add, info.usm_rows_needed, info.usm_rows, info.add_rows_needed, info.add_rows, info.defect_kind) == \
+            (n_store, n_mul, n_add, usm, usm, add, add, 0)
+        assert not bound_index.any() and bound_index.size == n_store
+        _, info = pkg.uint_traces_plan(rows_of(entries), m, a, log_usm=usm.bit_length() + 1, log_add=add.bit_length(), lib=lib)      # larger heights pad
+        assert (info.usm_rows_needed, info.usm_rows, info.add_rows_needed, info.add_rows) == (usm, 4 * usm, add, 2 * add)
+    bound_index, info = pkg.uint_traces_plan(rows_of(GOOD), *ops(3, 3), lib=lib)
+    assert [int(x) for x in bound_index] == [0, 1, 0, 0, 1, 1, 0] and (info.usm_rows_needed, info.add_rows_needed) == (32, 8)
+    # the Python layer sorts the store; handed over as it is, an unsorted one is refused (kind 4)
+    shuffled = [GOOD[i] for i in (3, 0, 6, 1, 2, 5, 4)]
+    bound_index, _ = pkg.uint_traces_plan(rows_of(shuffled), *ops(0, 0), lib=lib)
+    assert [int(x) for x in bound_index] == [0, 1, 0, 0, 1, 1, 0]
+    with pytest.raises(pkg.MidenHipError) as e:
+        pkg.uint_traces_plan(rows_of(shuffled), *ops(0, 0), lib=lib, sort=False)
+    assert (e.value.info.defect_kind, e.value.info.defect_index) == (4, 1)
+
+
+def test_empty_lists():
+    _, info = pkg.uint_traces_plan(rows_of([]), *ops(0, 0), lib=library())
+    assert (info.usm_rows_needed, info.add_rows_needed, info.usm_rows, info.add_rows, info.defect_kind) == (8, 2, 8, 2, 0)
+    usm = PT.uint_store_mul_trace(PT.UintStore(), PT.UintMulRequires(), PT.BytePairLutRequires())
+    add = PT.uint_add_trace(PT.UintAddRequires(), PT.UintStore())
+    assert usm.shape == (8, 44) and add.shape == (2, 30) and not add.any()
+    assert [int(x) for x in usm[:, PA.US_COL_PTR]] == [1, 1, 1, 1, 2, 2, 2, 2] and [int(x) for x in usm[:, PA.US_HUB_UINTVAL_MULT]] == [0, 1, 0, 0, 0, 1, 0, 0]
+    rows, m, a = PT.uint_lists(PT.UintStore())
+    assert (rows.size, m.size, a.size) == (0, 0, 0) and (rows.dtype, m.dtype, a.dtype) == (pkg.UINT_ROW_DTYPE, pkg.UINT_MUL_OP_DTYPE, pkg.UINT_ADD_OP_DTYPE)
+
+
+def refusal(entries, n_mul=0, n_add=0, log_usm=None, log_add=None):
+    m, a = ops(n_mul, n_add)
+    with pytest.raises(pkg.MidenHipError) as e:
+        pkg.uint_traces_plan(rows_of(entries), m, a, log_usm, log_add, lib=library(), sort=False)
+    info = e.value.info
+    assert (info.n_store, info.n_mul, info.n_add) == (len(entries), n_mul, n_add)
+    return info.defect_section, info.defect_kind, info.defect_index
+
+
+def edit(i, **kw):
+    rows = [dict(ptr=p, bound_ptr=b, value=v) for p, b, v in GOOD]
+    for j, f in ([(i, kw)] if not isinstance(i, list) else i):
+        rows[j].update(f)
+    return [(r["ptr"], r["bound_ptr"], r["value"]) for r in rows]
+
+
+def test_every_planner_refusal_names_section_kind_and_index():
+    lib = library()
+    lib.mh_uint_traces_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                        C.POINTER(pkg.UintTracesInfo)]
+    rows, (m, a) = rows_of(GOOD), ops(2, 2)
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+    # 1: a NULL pointer where a count is nonzero -- the store's before the multiplier's before the adder's; alone and with kind 4 behind it
+    info = pkg.UintTracesInfo()
+    for args, section in (((None, 7, None, 2, None, 2), 0), ((vp(rows), 7, None, 2, None, 2), 1), ((vp(rows), 7, vp(m), 2, None, 2), 2),
+                          ((vp(rows_of(edit(0, ptr=0))), 7, vp(m), 2, None, 2), 2)):
+        assert lib.mh_uint_traces_plan(*args, -1, -1, None, C.byref(info)) == 1
+        assert (info.defect_section, info.defect_kind, info.defect_index, info.n_store, info.n_mul, info.n_add) == (section, 1, 0, 7, 2, 2)
+    assert lib.mh_uint_traces_plan(None, 0, None, 0, None, 0, -1, -1, None, None) == 1
+    # 2: more than 2^24 rows in either trace (refused before a list is read), a log above 24, padding pointers reaching 2^32
+    for args, section, index in (((vp(rows), (1 << 22) + 1, None, 0, None, 0), 0, (1 << 22) + 1), ((vp(rows), 7, vp(m), (1 << 21) + 1, None, 0), 1, (1 << 21) + 1),
+                                 ((vp(rows), 7, None, 0, vp(a), (1 << 23) + 1), 2, (1 << 23) + 1)):
+        assert lib.mh_uint_traces_plan(*args, -1, -1, None, C.byref(info)) == 1
+        assert (info.defect_section, info.defect_kind, info.defect_index) == (section, 2, index)
+    assert refusal(GOOD, log_usm=25) == (0, 2, 25) and refusal(GOOD, log_add=25) == (2, 2, 25)
+    high = [(0xfffffffe, 0xfffffffe, 5)]                                       # one value, two blocks: the padding pointer is 2^32 - 1
+    _, info = pkg.uint_traces_plan(rows_of(high), *ops(0, 0), lib=lib)
+    assert info.usm_rows == 8
+    assert refusal(high, n_mul=2) == (0, 2, 3)                                 # 16 multiplier rows: four blocks, the second padding pointer is 2^32
+    assert refusal(high, log_usm=4) == (0, 2, 3)
+    assert refusal(high, log_usm=4, log_add=0, n_add=9) == (0, 2, 3)           # with kind 3 behind it
+    assert refusal([(0xffffffff, 0xffffffff, 5)]) == (0, 2, 1)
+    _, info = pkg.uint_traces_plan(rows_of([(0xfffffffc, 0xfffffffc, 5)]), *ops(2, 0), lib=lib)          # ... is 2^32 - 1
+    assert info.usm_rows == 16
+    # 3: a log below the height needed; index = the rows needed; the 44-column trace first
+    assert refusal(GOOD, n_mul=5, log_usm=5) == (0, 3, 64) and refusal(GOOD, n_add=5, log_add=3) == (2, 3, 16)
+    assert refusal(GOOD, n_mul=5, n_add=5, log_usm=0, log_add=0) == (0, 3, 64)
+    assert refusal(edit(0, ptr=0), n_add=5, log_add=3) == (2, 3, 16)           # with kind 4 behind it
+    assert refusal(GOOD, log_usm=-2) == (0, 3, 32)
+    # 4: ptr 0 or not above the one before -- the lowest index
+    assert refusal(edit(0, ptr=0)) == (0, 4, 0)
+    assert refusal(edit([(3, dict(ptr=7)), (5, dict(ptr=60000))])) == (0, 4, 3)
+    assert refusal(edit([(5, dict(ptr=59999)), (2, dict(bound_ptr=99))])) == (0, 4, 5)            # descending; with kind 6 behind it
+    # 5: a gap of 2^16 or more -- index: the row before it
+    assert refusal(edit(6, ptr=60001 + (1 << 16) + 1)) == (0, 5, 5)
+    assert refusal(edit([(4, dict(ptr=8 + (1 << 16) + 1)), (5, dict(ptr=2 * (1 << 16) + 10)), (6, dict(ptr=4 << 16))])) == (0, 5, 3)
+    assert refusal(edit([(6, dict(ptr=60001 + (1 << 16) + 1, value=1001))])) == (0, 5, 5)        # with kind 7 behind it
+    _, info = pkg.uint_traces_plan(rows_of(edit(6, ptr=60001 + (1 << 16))), *ops(0, 0), lib=lib)  # a gap of 2^16 - 1 is the largest
+    assert info.defect_kind == 0
+    # 6: a bound_ptr that is not stored
+    assert refusal(edit([(5, dict(bound_ptr=3)), (2, dict(bound_ptr=0))])) == (0, 6, 2)
+    assert refusal(edit([(4, dict(bound_ptr=60002)), (2, dict(value=1001))])) == (0, 6, 4)        # with kind 7 behind it
+    # 7: a value above its bound's -- a bound row above itself cannot be, a row above another row's value can
+    assert refusal(edit([(6, dict(value=1001)), (2, dict(value=1 << 200))])) == (0, 7, 2)
+    assert refusal(edit(1, bound_ptr=1)) == (0, 7, 1)                         # 2^256 - 1 under the bound 1000
+    _, info = pkg.uint_traces_plan(rows_of(edit(0, bound_ptr=2)), *ops(0, 0), lib=lib)            # 1000 under 2^256 - 1; rows 2, 3, 6 stay under 1000
+    assert info.defect_kind == 0
+
+
+@pytest.mark.parametrize("session", ["uint_arith_session(40)", "ec_add_session([0xb5, 77])"])
+def test_uint_lists_reproduces_the_reads_the_generators_recorded(session):
+    """After the generators have run, store.reads / limb_reads = the external reads `uint_lists` leaves + the reads the op lists imply.
+    The external reads of both sessions: one UintVal read of each of the five fixed rows (the verifier's boundary term)."""
+    if session.startswith("uint"):
+        _, traces, (_, (store, adds, muls)) = PT.uint_arith_session(40)
+    else:
+        _, traces, (_, (store, adds, muls, _ec, _ec_add)) = PT.ec_add_session([0xb5, 77])
+    rows, m, a = PT.uint_lists(store, adds, muls, own_reads_recorded=True)
+    assert [int(p) for p in rows["ptr"]] == sorted(store.rows) and m.size == len(muls.ops) and a.size == len(adds.ops)
+    assert [(int(r["ptr"]), int(r["val_reads"]), int(r["limb_reads"])) for r in rows if r["val_reads"] or r["limb_reads"]] == [(ptr, 1, 0) for ptr, _, _ in PA.FIXED_UINTS]
+    val = {int(r["ptr"]): int(r["val_reads"]) for r in rows}
+    limb = {int(r["ptr"]): int(r["limb_reads"]) for r in rows}
+    for o in m:
+        for f in ("a", "b", "bound"):
+            limb[int(o[f])] += 1
+        for f in ("c", "r"):
+            val[int(o[f])] += 1
+    for o in a:
+        for f in ("a", "b", "c", "bound"):
+            if int(o[f]):
+                val[int(o[f])] += 1
+    assert {p: n for p, n in val.items() if n} == store.reads and {p: n for p, n in limb.items() if n} == store.limb_reads
+    # ... and with the self-demand, the multiplicity columns of the session's trace
+    for r in rows:
+        val[int(r["bound_ptr"])] += 1
+    usm = traces[1]
+    n = rows.size
+    assert [int(x) for x in usm[1:4 * n:4, PA.US_HUB_UINTVAL_MULT]] == [val[int(p)] for p in rows["ptr"]]
+    assert [int(x) for x in usm[1:4 * n:4, PA.US_HUB_UINTLIMBS_MULT]] == [limb[int(p)] for p in rows["ptr"]]
+    # the records are the ledgers' entries
+    (ka, kc, pa, pb, pc_, pr, pbound, sub), mult = muls.ops[0]
+    assert tuple(int(x) for x in m[0]) == (pa, pb, pc_, pr, pbound, ka, kc, sub, mult)
+    (pa, pb, pc_, pbound, nz), mult = adds.ops[0]
+    assert tuple(int(x) for x in a[0]) == (pa, pb or 0, pc_ or 0, pbound, int(nz), 0, mult)
+    assert [int(x) for x in rows[0]["value"]] == PT._limbs(store.value(int(rows[0]["ptr"])), 32, 8)
+    bound_index, info = pkg.uint_traces_plan(rows, m, a, lib=library())
+    assert info.usm_rows_needed <= usm.shape[0] and all(int(rows["ptr"][b]) == int(bp) for b, bp in zip(bound_index, rows["bound_ptr"]))
+
+
+def test_abi_agrees_across_header_rust_python_and_library():
+    doc = open(os.path.join(ROOT, "include", "midenhip.h")).read()
+    h = re.sub(r"/\*.*?\*/", "", doc, flags=re.S)
+    rs = open(os.path.join(ROOT, "bindings", "rust", "midenhip_sys.rs")).read()
+    lib = library()
+    for f in FUNCS:
+        assert re.search(r"\bint\s+" + f + r"\s*\(", h), f
+        assert re.search(r"pub fn " + f + r"\s*\(", rs), f
+        assert f in pkg.EXPORTS, f
+        assert hasattr(lib, f), f
+    rust = lambda name: re.findall(r"pub (\w+): ([\w\[\]; ]+),", re.search(r"pub struct " + name + r" \{(.*?)\}", rs, flags=re.S).group(1))  # noqa: E731
+    rust_c = {"u32": "uint32_t", "u64": "uint64_t", "i32": "int32_t", "[u32; 8]": "uint32_t"}
+
+    def header(name):
+        body = re.search(r"typedef struct " + name + r" \{(.*?)\} " + name, h, flags=re.S).group(1)
+        return [(d.split()[0], n.strip().split("[")[0]) for d in body.split(";") if d.strip() for n in d.split(None, 1)[1].split(",")]
+    layouts = {
+        "mh_uint_row": (pkg.UINT_ROW_DTYPE, 48, ["ptr", "bound_ptr", "value", "val_reads", "limb_reads"], [0, 4, 8, 40, 44]),
+        "mh_uint_mul_op": (pkg.UINT_MUL_OP_DTYPE, 40, ["a", "b", "c", "r", "bound", "kappa_a", "kappa_c", "is_sub", "mult"], [0, 4, 8, 12, 16, 20, 24, 28, 32]),
+        "mh_uint_add_op": (pkg.UINT_ADD_OP_DTYPE, 32, ["a", "b", "c", "bound", "nz", "reserved", "mult"], [0, 4, 8, 12, 16, 20, 24]),
+    }
+    for name, (dt, size, names, offsets) in layouts.items():
+        assert re.search(r"typedef struct " + name + r" \{", h) and re.search(r"pub struct " + name + r" \{", rs), name
+        assert dt.itemsize == size and list(dt.names) == names and [dt.fields[n][1] for n in names] == offsets, name
+        assert [n for n, _ in rust(name)] == names and [(rust_c[t], n) for n, t in rust(name)] == header(name), name
+    info_fields = [("n_store", C.c_uint64), ("n_mul", C.c_uint64), ("n_add", C.c_uint64), ("usm_rows_needed", C.c_uint64), ("usm_rows", C.c_uint64),
+                   ("add_rows_needed", C.c_uint64), ("add_rows", C.c_uint64), ("defect_section", C.c_int32), ("defect_kind", C.c_int32),
+                   ("defect_index", C.c_uint64), ("defect_operand", C.c_int32), ("reserved", C.c_int32)]
+    assert pkg.UintTracesInfo._fields_ == info_fields and C.sizeof(pkg.UintTracesInfo) == 80 and pkg.UintTracesInfo.defect_index.offset == 64
+    ctype = {C.c_uint64: ("u64", "uint64_t"), C.c_int32: ("i32", "int32_t")}
+    assert rust("mh_uint_traces_info") == [(n, ctype[t][0]) for n, t in info_fields]
+    assert header("mh_uint_traces_info") == [(ctype[t][1], n) for n, t in info_fields]
+    args = lambda name: [x.split()[-1].lstrip("*") for x in re.search(r"\bint\s+" + name + r"\s*\((.*?)\);", h, flags=re.S).group(1).split(",")]  # noqa: E731
+    rargs = lambda name: re.findall(r"(\w+): ", re.search(r"pub fn " + name + r"\s*\((.*?)\)", rs, flags=re.S).group(1))  # noqa: E731
+    lists = ["rows", "n_store", "muls", "n_mul", "adds", "n_add", "log_usm", "log_add"]
+    assert args("mh_uint_traces_plan") == rargs("mh_uint_traces_plan") == lists + ["bound_index", "info"]
+    assert args("mh_uint_traces_build") == rargs("mh_uint_traces_build") == ["ctx"] + lists + ["usm_out", "add_out", "info"]
+    assert callable(pkg.uint_traces_plan) and callable(pkg.uint_traces) and callable(pkg.Precompile.uint_traces) and callable(PT.uint_lists)
+    sec = doc[doc.index("the precompile prover's UintStoreMul and UintAdd traces, built on the device"):]
+    assert "STRICTER than the reference's generator" in sec and "25 + 30 = 0 (mod 11)" in sec
+    assert "Not in scope" in sec
+    for word in ("interning", "computing r", "sorting the store", "EC point store", "MSM", "transcript-eval", "device-resident", "sharded", "2^24"):
+        assert word in sec[sec.index("Not in scope"):], word
