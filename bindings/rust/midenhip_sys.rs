@@ -341,6 +341,95 @@ pub struct mh_uint_traces_info {
     pub reserved: i32,
 }
 
+/// One row of the group table of mh_ec_traces_build (group pointer = row + 1): the uint pointers of a, b, the base-field bound and the
+/// scalar bound, and the reads of the row from outside the four EC chiplets (24 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_ec_group {
+    pub a_ptr: u32,
+    pub b_ptr: u32,
+    pub bound_ptr: u32,
+    pub sbound_ptr: u32,
+    pub ext_reads: u64,
+}
+
+/// One row of the point store (point pointer = row + 1): kind 0 member (trio u, w), 1 point at infinity, 2 closure-certified (32 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_ec_point {
+    pub group: u32,
+    pub x_ptr: u32,
+    pub y_ptr: u32,
+    pub u_ptr: u32,
+    pub w_ptr: u32,
+    pub kind: u32,
+    pub ext_reads: u64,
+}
+
+/// p + q = r over point pointers: kind 0 pai_p, 1 pai_q, 2 pai_both, 3 cancel, 4 double, 5 generic; t = slope_aux, lambda, t, y3, e, x3
+/// (56 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_ec_add_op {
+    pub group: u32,
+    pub p: u32,
+    pub q: u32,
+    pub r: u32,
+    pub kind: u32,
+    pub mints: u32,
+    pub t: [u32; 6],
+    pub mult: u64,
+}
+
+/// One MSM expression (pointer = index + 1): kind 0 intro, 1 combine, 2 neg (48 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_msm_expr {
+    pub kind: u32,
+    pub group: u32,
+    pub val: u32,
+    pub a_expr: u32,
+    pub b_expr: u32,
+    pub n_rows: u32,
+    pub neg_minted: u32,
+    pub reserved: u32,
+    pub ext_mult: u64,
+    pub claim_mult: u64,
+}
+
+/// One term row of an MSM expression: the base's point pointer and the scalar's uint pointer (8 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_msm_term {
+    pub base: u32,
+    pub scalar: u32,
+}
+
+/// mh_ec_traces_plan / mh_ec_traces_build: the lists' sizes, the least heights and the ones taken, and the defect that refused the call:
+/// section 0 groups, 1 points, 2 add, 3 msm; kind 0 none, 1..7 the planner's, 8..15 the device's checking pass (see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_ec_traces_info {
+    pub n_groups: u64,
+    pub n_points: u64,
+    pub n_add: u64,
+    pub n_exprs: u64,
+    pub n_terms: u64,
+    pub groups_rows_needed: u64,
+    pub groups_rows: u64,
+    pub points_rows_needed: u64,
+    pub points_rows: u64,
+    pub add_rows_needed: u64,
+    pub add_rows: u64,
+    pub msm_rows_needed: u64,
+    pub msm_rows: u64,
+    pub defect_section: i32,
+    pub defect_kind: i32,
+    pub defect_index: u64,
+    pub defect_operand: i32,
+    pub reserved: i32,
+}
+
 /// An encoded denominator whose net multiplicity is not zero (mh_check_balance*; the reference's `Unmatched`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -751,4 +840,6 @@ unsafe extern "C" {
     pub fn mh_poseidon2_chiplet_trace_build(ctx: *mut mh_ctx, abs: *const mh_p2c_absorption, n_abs: usize, blocks: *const u64, refs: *const i64, n_cycles: usize, log_n: c_int, out: *mut *mut mh_trace, digests: *mut u64, outputs: *mut u64, info: *mut mh_p2c_info) -> c_int;
     pub fn mh_uint_traces_plan(rows: *const mh_uint_row, n_store: usize, muls: *const mh_uint_mul_op, n_mul: usize, adds: *const mh_uint_add_op, n_add: usize, log_usm: c_int, log_add: c_int, bound_index: *mut u32, info: *mut mh_uint_traces_info) -> c_int;
     pub fn mh_uint_traces_build(ctx: *mut mh_ctx, rows: *const mh_uint_row, n_store: usize, muls: *const mh_uint_mul_op, n_mul: usize, adds: *const mh_uint_add_op, n_add: usize, log_usm: c_int, log_add: c_int, usm_out: *mut *mut mh_trace, add_out: *mut *mut mh_trace, info: *mut mh_uint_traces_info) -> c_int;
+    pub fn mh_ec_traces_plan(groups: *const mh_ec_group, n_groups: usize, points: *const mh_ec_point, n_points: usize, adds: *const mh_ec_add_op, n_add: usize, exprs: *const mh_msm_expr, n_exprs: usize, terms: *const mh_msm_term, n_terms: usize, log_groups: c_int, log_points: c_int, log_add: c_int, log_msm: c_int, row_start: *mut u32, info: *mut mh_ec_traces_info) -> c_int;
+    pub fn mh_ec_traces_build(ctx: *mut mh_ctx, groups: *const mh_ec_group, n_groups: usize, points: *const mh_ec_point, n_points: usize, adds: *const mh_ec_add_op, n_add: usize, exprs: *const mh_msm_expr, n_exprs: usize, terms: *const mh_msm_term, n_terms: usize, log_groups: c_int, log_points: c_int, log_add: c_int, log_msm: c_int, groups_out: *mut *mut mh_trace, points_out: *mut *mut mh_trace, add_out: *mut *mut mh_trace, msm_out: *mut *mut mh_trace, info: *mut mh_ec_traces_info) -> c_int;
 }

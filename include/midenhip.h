@@ -1473,6 +1473,97 @@ int mh_uint_traces_build(mh_ctx* ctx, const mh_uint_row* rows, size_t n_store, c
                          const mh_uint_add_op* adds, size_t n_add, int log_usm, int log_add /* -1: least */,
                          mh_trace** usm_out /* width 44 */, mh_trace** add_out /* width 30 */, mh_uint_traces_info* info /* may be NULL */);
 
+/* ---- the precompile prover's EcGroups, EcPointStore, EcGroupAdd and EcMsm traces, built on the device from the ledgers ----
+ * mh_ec_traces_build takes the group table, the point store, the recorded additions and the MSM expressions with their term rows, all
+ * as pointer lists (no coordinate limb enters these traces), and returns the main traces of EcGroupsAir (6 columns, index 8),
+ * EcPointStoreAir (14, index 9), EcGroupAddAir (21, index 10) and EcMsmAir (38, index 11 of mh_prove_precompile_traces,
+ * mh_check_precompile_traces and mh_fill_multiplicities_precompile_traces), device-resident.  Device stage: csrc/ec_traces.hip (row
+ * bodies: csrc/ec_traces_rows.cuh); the planner (mh_ec_traces_plan, host only): csrc/ec_traces_plan.cpp.  The rule is the reference's
+ * (ec/trace.rs:347-411, ec/add/trace.rs:146-251, ec/msm/trace.rs:390-500) and is fixed.
+ *   groups    mh_ec_group, row i is group pointer i + 1: the uint pointers of a, b, the base-field bound and the scalar bound (the bound
+ *             itself where the group has no other).  Trace row: ptr, a_ptr, b_ptr, bound_ptr, sbound_ptr, mult.  Pads run the pointer
+ *             chain on, the other cells 0.
+ *   points    mh_ec_point, row i is point pointer i + 1: group, x_ptr, y_ptr, the membership trio's u_ptr, w_ptr, and kind 0 member,
+ *             1 point at infinity (all four pointers 0), 2 closure-certified (u, w 0).  Trace row: ptr, group, the group's a, b, bound,
+ *             sbound, x, y, u, w, is_pai, ECPOINT_MULT, 1, is_cert.  Pads all zero.
+ *   add       mh_ec_add_op: group, the point pointers p, q, r, kind 0 pai_p, 1 pai_q, 2 pai_both, 3 cancel, 4 double, 5 generic, mints
+ *             (r is minted by this addition: double / generic only), t = slope_aux, lambda, t, y3, e, x3 (uint pointers, 0 in the dead
+ *             cases) and mult, the relation's multiplicity (the host's: relations are deduplicated there).  Four rows per addition, cells
+ *             0..2: t[0..2] | t[3..5] | r, sbound, group | mult mod p, p, q; columns 3..20 on all four: px, py, qx, qy (the operands'
+ *             x_ptr, y_ptr; 0 for the point at infinity), the group's a, b, bound, the five case flags, 1, mints, and for mints
+ *             r - p - 1 and r - q - 1 in 16-bit halves.  All-zero blocks after the additions.
+ *   msm       mh_msm_expr, expression k is pointer k + 1: kind 0 intro, 1 combine, 2 neg; group; val (the value point); a_expr, b_expr
+ *             (operands: earlier expressions; 0 where the kind has none); n_rows; neg_minted; ext_mult; claim_mult.  mh_msm_term: the
+ *             expressions' (base, scalar) rows, concatenated in expression order, bases strictly ascending within an expression.  One
+ *             trace row per term; the other 36 cells are derived: a combine row with base B has i, j = the lower bounds of B in the
+ *             operands' term lists, take_a / take_b / take_both by which of them hold B, base_a, s_a, base_b, s_b the operands' terms at
+ *             the cursors (0 on a side not taken); a neg row has i = idx and the operand's row; val_a, val_b the operands' val; neg_x,
+ *             neg_ya val_a's coordinates and neg_yr val's y on a neg's boundary row; the 16-bit halves of expr - a_expr - 1 and
+ *             expr - b_expr - 1 on boundary rows.  Pads: expr_ptr = n_exprs + 1, idx counting from 0.
+ *   demand    computed on the device, all mod p.  Group mult = ext_reads + one per point of the group + one per cancel / double / generic
+ *             addition + one per combine / neg expression.  ECPOINT_MULT = ext_reads + p and q of every addition + r of every cancel /
+ *             double / generic addition + val_a and val of every neg expression.  Expression mult = ext_mult + one per use as a_expr or
+ *             b_expr (combine(a, a) uses a twice).  ext_reads / ext_mult are the reads from OUTSIDE these four chiplets (the verifier's
+ *             boundary read of the fixed groups, the eval chip's point_on_group / pai_on_group / resolve reads, EcRequire.neg's read of
+ *             the point at infinity): any 64-bit word, reduced mod p here.  The intro rows' read of the literal 1 is a val_reads of
+ *             mh_uint_row (above); the Range16 reads of the ordering limbs are mh_fill_multiplicities*'s, as in the uint build.
+ *   heights   groups, points: max(2, next_pow2(n)); add: next_pow2(4 max(1, n_add)); msm: max(2, next_pow2(n_terms)).  log_* = -1
+ *             takes them; a larger one pads; a smaller one is refused.
+ *   refusals  MH_ERR_INVALID, the out pointers untouched, no trace allocated, `info` filled, mh_last_error names section (0 groups,
+ *             1 points, 2 add, 3 msm), kind, index and operand; the lowest kind first, within it the lowest section, then the lowest
+ *             index; a later kind is only looked for once the earlier ones are absent.  Found by the planner: 1 a NULL list where a count
+ *             is nonzero (section 3: operand 0 exprs, 1 terms); 2 more than 2^24 rows in a trace (index: the count) or a log_* above 24
+ *             (index: the log); 3 a log_* below the height needed (index: the rows needed); 4 a point's group that is 0 or above
+ *             n_groups; 5 a point kind outside 0..2 (operand 0), a point at infinity with a nonzero x, y, u or w (operand 1..4), a
+ *             certified point with a nonzero u or w (operand 3, 4); 6 an expression kind outside 0..2 (operand 0), n_rows = 0 or an
+ *             intro with n_rows != 1 (operand 1), the n_rows not summing to n_terms (index n_exprs, operand 2); 7 an operand that is 0
+ *             or not an earlier expression, or nonzero where the kind has none (operand 0 a_expr, 1 b_expr).  Found by the device's
+ *             checking pass, through one packed 64-bit minimum read back once before any trace is allocated: 8 an addition's p, q, r or
+ *             group (operand 0..3), or an expression's val or group (operand 0, 1), that is 0 or out of range; 9 an addition kind
+ *             outside 0..5 (operand 0), mints outside {0, 1} or on a kind other than double / generic (operand 1); 10 p, q or r of an
+ *             addition stored under another group than the op's (operand 0..2), or an expression whose group is not its val's (operand
+ *             0), its a_expr's (1) or its b_expr's (2); 11 an addition whose kind disagrees with which of p, q are points at infinity;
+ *             12 mints with r <= p (operand 0), r <= q (1) or an r that is not a certified row (2); 13 a term row whose base is not above
+ *             the one before it in its expression (index: the term row); 14 (index: the term row) a combine row whose base neither
+ *             operand holds (operand 0), a merge that skips an operand's term -- this row's cursors advanced by its takes are not the
+ *             next row's, the first row's are not 0, 0, or the last row does not end at both lists' lengths (operand 1) --, a neg whose
+ *             rows are not its operand's bases one for one (operand 2); 15 an intro whose val is not its base.  Sections 0..2 index
+ *             their record, section 3 the expression (kinds 6..8, 10, 15) or the term row (13, 14).
+ *             The recorders (EcRequire.add, EcMsmRequires of the reference's ec/require.rs and ec/msm/require.rs) can produce none of
+ *             these: every check here is of a pointer, a kind or an order, none of a value -- equal values need not be equal pointers
+ *             (pinned uints exist).
+ * Every cell of all four traces is written by the call, padding included; the counters and the minimum are scratch the call clears
+ * itself; a second call leaves the same bytes.
+ * Not in scope: interning, deduplication and the 256-bit arithmetic of the group law (the host recorder's and the uint build's); the
+ * TranscriptEval and ChunkNode traces; device-resident inputs; sharded contexts; more than 2^24 rows. */
+typedef struct mh_ec_group { uint32_t a_ptr, b_ptr, bound_ptr, sbound_ptr; uint64_t ext_reads; } mh_ec_group;                      /* 24 bytes */
+typedef struct mh_ec_point { uint32_t group, x_ptr, y_ptr, u_ptr, w_ptr, kind; uint64_t ext_reads; } mh_ec_point;                  /* 32 bytes */
+typedef struct mh_ec_add_op { uint32_t group, p, q, r, kind, mints; uint32_t t[6]; uint64_t mult; } mh_ec_add_op;                  /* 56 bytes */
+typedef struct mh_msm_expr { uint32_t kind, group, val, a_expr, b_expr, n_rows, neg_minted, reserved; uint64_t ext_mult, claim_mult; } mh_msm_expr; /* 48 bytes */
+typedef struct mh_msm_term { uint32_t base, scalar; } mh_msm_term;                                                                 /* 8 bytes */
+typedef struct mh_ec_traces_info {
+  uint64_t n_groups, n_points, n_add, n_exprs, n_terms;
+  uint64_t groups_rows_needed, groups_rows;   /* the least height, and the one taken */
+  uint64_t points_rows_needed, points_rows;
+  uint64_t add_rows_needed, add_rows;
+  uint64_t msm_rows_needed, msm_rows;
+  int32_t defect_section;                     /* 0 groups, 1 points, 2 add, 3 msm */
+  int32_t defect_kind;                        /* 0 none */
+  uint64_t defect_index;
+  int32_t defect_operand;
+  int32_t reserved;
+} mh_ec_traces_info;                          /* 128 bytes */
+/* Host only: kinds 1..7, the heights, and every expression's first term row. */
+int mh_ec_traces_plan(const mh_ec_group* groups, size_t n_groups, const mh_ec_point* points, size_t n_points, const mh_ec_add_op* adds,
+                      size_t n_add, const mh_msm_expr* exprs, size_t n_exprs, const mh_msm_term* terms, size_t n_terms, int log_groups,
+                      int log_points, int log_add, int log_msm /* -1: least */, uint32_t* row_start /* [n_exprs] or NULL */,
+                      mh_ec_traces_info* info);
+int mh_ec_traces_build(mh_ctx* ctx, const mh_ec_group* groups, size_t n_groups, const mh_ec_point* points, size_t n_points,
+                       const mh_ec_add_op* adds, size_t n_add, const mh_msm_expr* exprs, size_t n_exprs, const mh_msm_term* terms,
+                       size_t n_terms, int log_groups, int log_points, int log_add, int log_msm /* -1: least */,
+                       mh_trace** groups_out /* width 6 */, mh_trace** points_out /* width 14 */, mh_trace** add_out /* width 21 */,
+                       mh_trace** msm_out /* width 38 */, mh_ec_traces_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

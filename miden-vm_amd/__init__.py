@@ -47,6 +47,7 @@ EXPORTS = [
     "mh_kernel_rom_section_build", "mh_miden_kernel_rom_section", "mh_miden_chiplets_build", "mh_miden_chiplets_frame",
     "mh_keccak_round_program", "mh_keccak_round_levels", "mh_keccak_round_trace_build", "mh_keccak_traces_build",
     "mh_poseidon2_chiplet_plan", "mh_poseidon2_chiplet_trace_build", "mh_uint_traces_plan", "mh_uint_traces_build",
+    "mh_ec_traces_plan", "mh_ec_traces_build",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
@@ -797,6 +798,77 @@ def uint_traces(ctx, rows, muls, adds, log_usm=None, log_add=None, sort=True):
     return (Trace.from_handle(ctx, hu, int(info.usm_rows).bit_length() - 1, 44), Trace.from_handle(ctx, ha, int(info.add_rows).bit_length() - 1, 30), info)
 
 
+# ---- the precompile prover's EcGroups, EcPointStore, EcGroupAdd and EcMsm traces (include/midenhip.h mh_ec_traces_plan, mh_ec_traces_build) ----
+EC_GROUP_DTYPE = np.dtype([("a_ptr", "<u4"), ("b_ptr", "<u4"), ("bound_ptr", "<u4"), ("sbound_ptr", "<u4"), ("ext_reads", "<u8")])             # mh_ec_group
+EC_POINT_DTYPE = np.dtype([("group", "<u4"), ("x_ptr", "<u4"), ("y_ptr", "<u4"), ("u_ptr", "<u4"), ("w_ptr", "<u4"), ("kind", "<u4"),
+                           ("ext_reads", "<u8")])                                                                                              # mh_ec_point
+EC_ADD_OP_DTYPE = np.dtype([("group", "<u4"), ("p", "<u4"), ("q", "<u4"), ("r", "<u4"), ("kind", "<u4"), ("mints", "<u4"), ("t", "<u4", (6,)),
+                            ("mult", "<u8")])                                                                                                  # mh_ec_add_op
+MSM_EXPR_DTYPE = np.dtype([("kind", "<u4"), ("group", "<u4"), ("val", "<u4"), ("a_expr", "<u4"), ("b_expr", "<u4"), ("n_rows", "<u4"),
+                           ("neg_minted", "<u4"), ("reserved", "<u4"), ("ext_mult", "<u8"), ("claim_mult", "<u8")])                            # mh_msm_expr
+MSM_TERM_DTYPE = np.dtype([("base", "<u4"), ("scalar", "<u4")])                                                                                # mh_msm_term
+
+
+class EcTracesInfo(C.Structure):
+    """mh_ec_traces_info: the lists' sizes, the least heights of the four traces and the ones taken; `defect_section` 0 groups, 1 points,
+    2 add, 3 msm; `defect_kind` 0 none, 1..7 the planner's (a NULL list; too many rows or a log above 24; log below the height, index the
+    rows needed; a point's group out of range; a point kind or its pointers; an expression's kind or n_rows; an operand that is not an
+    earlier expression), 8..15 the device's (a pointer out of range, operand named; an addition's kind or mints; another group; the kind
+    against the points at infinity; a mint's ordering; bases not ascending; a merge or neg that does not follow its operands; an intro
+    whose val is not its base)."""
+    _fields_ = [("n_groups", C.c_uint64), ("n_points", C.c_uint64), ("n_add", C.c_uint64), ("n_exprs", C.c_uint64), ("n_terms", C.c_uint64),
+                ("groups_rows_needed", C.c_uint64), ("groups_rows", C.c_uint64), ("points_rows_needed", C.c_uint64), ("points_rows", C.c_uint64),
+                ("add_rows_needed", C.c_uint64), ("add_rows", C.c_uint64), ("msm_rows_needed", C.c_uint64), ("msm_rows", C.c_uint64),
+                ("defect_section", C.c_int32), ("defect_kind", C.c_int32), ("defect_index", C.c_uint64), ("defect_operand", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def __repr__(self):
+        return "EcTracesInfo(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_ if n != "reserved") + ")"
+
+
+_EC_LIST_DTYPES = (EC_GROUP_DTYPE, EC_POINT_DTYPE, EC_ADD_OP_DTYPE, MSM_EXPR_DTYPE, MSM_TERM_DTYPE)
+
+
+def _ec_call_args(lists, logs):
+    """the five record arrays, and the ABI's arguments for them and the four logs"""
+    recs = [_records(x, dt) for x, dt in zip(lists, _EC_LIST_DTYPES)]
+    args = [v for r in recs for v in (_void_p(r), r.size)] + [-1 if l is None else int(l) for l in logs]
+    return recs, args
+
+
+def ec_traces_plan(groups, points, adds, exprs, terms, log_groups=-1, log_points=-1, log_add=-1, log_msm=-1, lib=None):
+    """mh_ec_traces_plan (host only): validates what one record shows and gives the heights -> (row_start uint32 [n_exprs], EcTracesInfo).
+    EC_GROUP_DTYPE, EC_POINT_DTYPE, EC_ADD_OP_DTYPE, MSM_EXPR_DTYPE, MSM_TERM_DTYPE records.  A defect raises MidenHipError with `e.info`."""
+    lib = lib or load_library()
+    recs, args = _ec_call_args((groups, points, adds, exprs, terms), (log_groups, log_points, log_add, log_msm))
+    row_start, info = np.zeros(recs[3].size, dtype=np.uint32), EcTracesInfo()
+    lib.mh_ec_traces_plan.argtypes = [C.c_void_p, C.c_size_t] * 5 + [C.c_int] * 4 + [C.c_void_p, C.POINTER(EcTracesInfo)]
+    rc = lib.mh_ec_traces_plan(*args, _void_p(row_start), C.byref(info))
+    if rc != 0:
+        e = MidenHipError(f"mh_ec_traces_plan: section {info.defect_section}, defect {info.defect_kind}, index {info.defect_index}, "
+                          f"operand {info.defect_operand}")
+        e.info = info
+        raise e
+    return row_start, info
+
+
+def ec_traces(ctx, groups, points, adds, exprs, terms, log_groups=-1, log_points=-1, log_add=-1, log_msm=-1):
+    """mh_ec_traces_build: EcGroupsAir's, EcPointStoreAir's, EcGroupAddAir's and EcMsmAir's main traces on the device from the ledgers --
+    `groups` EC_GROUP_DTYPE (row i is group i + 1), `points` EC_POINT_DTYPE (row i is point i + 1; kind 0 member, 1 point at infinity,
+    2 closure-certified), `adds` EC_ADD_OP_DTYPE (kind 0 pai_p .. 5 generic), `exprs` MSM_EXPR_DTYPE (kind 0 intro, 1 combine, 2 neg) and
+    `terms` MSM_TERM_DTYPE (the expressions' rows, concatenated) -> ((Trace [., 6], Trace [., 14], Trace [., 21], Trace [., 38]),
+    EcTracesInfo).  ext_reads / ext_mult are the reads from outside the four chiplets; the device adds the rest.  log_* -1 (or None): the
+    least heights.  A refusal raises MidenHipError with `e.info` (section, kind, index, operand)."""
+    recs, args = _ec_call_args((groups, points, adds, exprs, terms), (log_groups, log_points, log_add, log_msm))
+    lib = ctx.lib
+    lib.mh_ec_traces_build.argtypes = [C.c_void_p] + [C.c_void_p, C.c_size_t] * 5 + [C.c_int] * 4 + [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(EcTracesInfo)]
+    hs, info = [C.c_void_p() for _ in range(4)], EcTracesInfo()
+    rc = lib.mh_ec_traces_build(ctx.h, *args, *[C.byref(h) for h in hs], C.byref(info))
+    _mem_section_result(lib, ctx, rc, info)
+    rows = (info.groups_rows, info.points_rows, info.add_rows, info.msm_rows)
+    return tuple(Trace.from_handle(ctx, h, int(n).bit_length() - 1, w) for h, n, w in zip(hs, rows, (6, 14, 21, 38))), info
+
+
 def load_library():
     """dlopen libmidenhip.so (does not touch the GPU)."""
     global _lib
@@ -893,6 +965,10 @@ class Ctx:
             self.close()
         except Exception:
             pass
+
+    def ec_traces(self, groups, points, adds, exprs, terms, log_groups=-1, log_points=-1, log_add=-1, log_msm=-1):
+        """ec_traces on this context: the session's traces 8..11 (EcGroups, EcPointStore, EcGroupAdd, EcMsm) from the EC ledgers."""
+        return ec_traces(self, groups, points, adds, exprs, terms, log_groups, log_points, log_add, log_msm)
 
     # ---- profiler ----
     def prof_enable(self, on=True):
@@ -2344,6 +2420,10 @@ class Precompile:
     def uint_traces(self, rows, muls, adds, log_usm=None, log_add=None):
         """uint_traces on this object's context: the session's traces 6 (UintStoreMul) and 7 (UintAdd) from the uint ledgers."""
         return uint_traces(self.ctx, rows, muls, adds, log_usm, log_add)
+
+    def ec_traces(self, groups, points, adds, exprs, terms, log_groups=-1, log_points=-1, log_add=-1, log_msm=-1):
+        """ec_traces on this object's context: the session's traces 8..11 (EcGroups, EcPointStore, EcGroupAdd, EcMsm) from the EC ledgers."""
+        return ec_traces(self.ctx, groups, points, adds, exprs, terms, log_groups, log_points, log_add, log_msm)
 
     def keccak_traces(self, messages, chunk_heads, log_round=None, log_sponge=None, want_digests=False):
         """keccak_traces on this object's context: the session's traces 2 (Keccak round) and 4 (Keccak sponge) from the messages."""

@@ -24,6 +24,7 @@
 // the one in hand).  The counters and the minimum are scratch that the call clears itself; every cell of both traces has exactly one
 // writer: a second call leaves the same bytes.
 #include "section_out.cuh"
+#include "wave_count.cuh"
 #include <vector>
 
 static_assert(sizeof(mh_uint_row) == 48, "mh_uint_row is 48 bytes");
@@ -73,23 +74,8 @@ UT_HD void ut_report(unsigned long long* defect, int kind, int section, u32 inde
 #endif
 }
 
-// One read of a store row.  Most relations of a session share their bound, and many an operand (the x of a Horner evaluation): a lane
-// per relation would send a wave's 64 atomics to ONE address, and they serialise (measured: 0.56 ms for 49 159 rows that read one
-// bound).  So the lanes of the wave that are here compare their counter with the first lane's; those that agree add once, the rest add
-// for themselves.
-UT_HD void ut_count(u32* counter) {
-#ifdef __HIP_DEVICE_COMPILE__
-  const unsigned long long here = __ballot(1);
-  const int first = __ffsll(here) - 1;
-  const unsigned long long mine = (unsigned long long)counter;
-  const unsigned long long lead = ((unsigned long long)(u32)__shfl((int)(mine >> 32), first) << 32) | (u32)__shfl((int)(u32)mine, first);
-  const unsigned long long same = __ballot(mine == lead);
-  if (mine != lead) atomicAdd(counter, 1u);
-  else if ((int)__lane_id() == first) atomicAdd(counter, (u32)__popcll(same));
-#else
-  ++*counter;
-#endif
-}
+// One read of a store row: agreeing lanes of a wave add once (wave_count.cuh)
+UT_HD void ut_count(u32* counter) { wave_count(counter); }
 
 UT_HD void ut_load(u32 (&v)[8], const mh_uint_row* rows, u32 index) {
 #pragma unroll

@@ -1405,6 +1405,59 @@ def ec_msm_trace(msm, store, bpl, min_height=0):
     return t
 
 
+def ec_lists(ec, ec_add, msm=None, own_reads_recorded=False):
+    """The ledgers as mh_ec_traces_build takes them -> (groups, points, adds, exprs, terms) record arrays (EC_GROUP_DTYPE, EC_POINT_DTYPE,
+    EC_ADD_OP_DTYPE, MSM_EXPR_DTYPE, MSM_TERM_DTYPE).  ext_reads / ext_mult are the reads from OUTSIDE the four chiplets: the demand as it
+    stands less what the recorders added for the chiplets themselves (a point's read of its group, a combine's / neg's of the group, a
+    neg's of the two value points, an expression's use as an operand) and -- own_reads_recorded=True, after `ec_group_add_trace` has
+    routed its consumes -- less the reads the additions imply (the device adds all of those back)."""
+    from .. import EC_GROUP_DTYPE, EC_POINT_DTYPE, EC_ADD_OP_DTYPE, MSM_EXPR_DTYPE, MSM_TERM_DTYPE
+    ops, exprs = (ec_add.ops if ec_add is not None else []), (msm.exprs if msm is not None else [])
+    own_group, own_point, own_expr = {}, {}, {}
+
+    def bump(d, key):
+        d[key] = d.get(key, 0) + 1
+    for group, _binding in ec.points:
+        bump(own_group, group)
+    for e in exprs:
+        if e["kind"] != "intro":
+            bump(own_group, e["group"])
+            bump(own_expr, e["a_expr"])
+        if e["kind"] == "combine":
+            bump(own_expr, e["b_expr"])
+        if e["kind"] == "neg":
+            bump(own_point, e["val_a"])
+            bump(own_point, e["val"])
+    if own_reads_recorded:
+        for op, _ in ops:
+            bump(own_point, op["p"])
+            bump(own_point, op["q"])
+            if op["case"] in ("cancel", "double", "generic"):
+                bump(own_group, op["group"])
+                bump(own_point, op["r"])
+
+    def word(mult, own=0):
+        assert int(mult) >= own, "the demand holds less than the chiplets' own reads"
+        return int(mult) - own if int(mult) - own < 1 << 64 else (int(mult) - own) % P
+    groups = np.array([(a, bp, bound, ec.group_sbound(i + 1), word(ec.group_demand.get(i + 1, 0), own_group.get(i + 1, 0)))
+                       for i, (a, bp, bound, _sb) in enumerate(ec.groups)], dtype=EC_GROUP_DTYPE).reshape(-1)
+    point_rows = []
+    for i, (group, binding) in enumerate(ec.points):
+        x, y, membership = (0, 0, None) if binding is None else binding
+        u, w = membership or (0, 0)
+        point_rows.append((group, x, y, u, w, 1 if binding is None else 2 if membership is None else 0,
+                           word(ec.point_demand.get(i + 1, 0), own_point.get(i + 1, 0))))
+    points = np.array(point_rows, dtype=EC_POINT_DTYPE).reshape(-1)
+    cases = ("pai_p", "pai_q", "pai_both", "cancel", "double", "generic")
+    adds = np.array([(op["group"], op["p"], op["q"], op["r"], cases.index(op["case"]), int(op["mints"]), tuple(op["transients"] or [0] * 6), word(mult))
+                     for op, mult in ops], dtype=EC_ADD_OP_DTYPE).reshape(-1)
+    kinds = ("intro", "combine", "neg")
+    expr_rec = np.array([(kinds.index(e["kind"]), e["group"], e["val"], e["a_expr"], e["b_expr"], len(e["rows"]), e["neg_minted"], 0,
+                          word(e["mult"], own_expr.get(k + 1, 0)), word(e["claim_mult"])) for k, e in enumerate(exprs)], dtype=MSM_EXPR_DTYPE).reshape(-1)
+    terms = np.array([(r["base"], r["scalar"]) for e in exprs for r in e["rows"]], dtype=MSM_TERM_DTYPE).reshape(-1)
+    return groups, points, adds, expr_rec, terms
+
+
 class TranscriptEvalRequires:
     """`TranscriptEvalRequires` (transcript/eval/trace.rs:294-893): the transcript DAG as it is recorded -- `Truthy` handles (linear: each is
     consumed exactly once, by an AND or as the root), uint and EC value nodes (deduplicated, consumed by their readers' count), every node's
