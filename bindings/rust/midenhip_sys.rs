@@ -430,6 +430,79 @@ pub struct mh_ec_traces_info {
     pub reserved: i32,
 }
 
+/// One distinct hashed input of mh_chunk_node_trace_build: where its bytes lie, its chunk chain and sponge rows, the first cycle of the
+/// chain's absorption, the one-block absorptions of its digest and of the node, and the node's readers (64 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_kn_record {
+    pub offset: u64,
+    pub len: u64,
+    pub chunk_head: u64,
+    pub sponge_head: u64,
+    pub perm_chunks: u64,
+    pub perm_digest_chunks: u64,
+    pub perm_keccak: u64,
+    pub out_mult: u64,
+}
+
+/// mh_chunk_node_plan / mh_chunk_node_trace_build: sizes, the least height and the one taken, and the defect that refused the call: kind
+/// 0 none, 1..7 the planner's, 8, 9 the device's checking pass (see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_chunk_node_info {
+    pub n_records: u64,
+    pub n_chunks: u64,
+    pub p2_cycles: u64,
+    pub rows_needed: u64,
+    pub rows: u64,
+    pub defect_kind: i32,
+    pub defect_operand: i32,
+    pub defect_index: u64,
+}
+
+/// One node of the transcript for mh_transcript_eval_trace_build: kind 0 ZERO, 1 AND, 2 UINT_LEAF, 3 UINT_PIN, 4 UINT_OP, 5 EC_CREATE,
+/// 6 EC_PAI, 7 EC_OP, 8 EC_MSM; lhs / rhs a node index below the own, -1 - cycle for an external True binding, a literal index, or an
+/// MSM's term_start / n_terms (64 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_te_node {
+    pub kind: u32,
+    pub op: u32,
+    pub lhs: i64,
+    pub rhs: i64,
+    pub perm: u64,
+    pub ptr: u64,
+    pub bound_ptr: u64,
+    pub group: u64,
+    pub expr: u64,
+}
+
+/// One term row of an MSM claim: the node indices of its base and its scalar (8 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_te_term {
+    pub base_node: u32,
+    pub scalar_node: u32,
+}
+
+/// mh_transcript_eval_plan / mh_transcript_eval_trace_build: sizes, the active rows, the ZERO nodes other than the root, the heights and
+/// the defect that refused the call: kind 0 none, 1..7 the planner's, 8..15 the device's checking pass (see midenhip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct mh_transcript_eval_info {
+    pub n_nodes: u64,
+    pub n_terms: u64,
+    pub n_lit: u64,
+    pub p2_cycles: u64,
+    pub active_rows: u64,
+    pub n_zero: u64,
+    pub rows_needed: u64,
+    pub rows: u64,
+    pub defect_kind: i32,
+    pub defect_operand: i32,
+    pub defect_index: u64,
+}
+
 /// An encoded denominator whose net multiplicity is not zero (mh_check_balance*; the reference's `Unmatched`).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -842,4 +915,8 @@ unsafe extern "C" {
     pub fn mh_uint_traces_build(ctx: *mut mh_ctx, rows: *const mh_uint_row, n_store: usize, muls: *const mh_uint_mul_op, n_mul: usize, adds: *const mh_uint_add_op, n_add: usize, log_usm: c_int, log_add: c_int, usm_out: *mut *mut mh_trace, add_out: *mut *mut mh_trace, info: *mut mh_uint_traces_info) -> c_int;
     pub fn mh_ec_traces_plan(groups: *const mh_ec_group, n_groups: usize, points: *const mh_ec_point, n_points: usize, adds: *const mh_ec_add_op, n_add: usize, exprs: *const mh_msm_expr, n_exprs: usize, terms: *const mh_msm_term, n_terms: usize, log_groups: c_int, log_points: c_int, log_add: c_int, log_msm: c_int, row_start: *mut u32, info: *mut mh_ec_traces_info) -> c_int;
     pub fn mh_ec_traces_build(ctx: *mut mh_ctx, groups: *const mh_ec_group, n_groups: usize, points: *const mh_ec_point, n_points: usize, adds: *const mh_ec_add_op, n_add: usize, exprs: *const mh_msm_expr, n_exprs: usize, terms: *const mh_msm_term, n_terms: usize, log_groups: c_int, log_points: c_int, log_add: c_int, log_msm: c_int, groups_out: *mut *mut mh_trace, points_out: *mut *mut mh_trace, add_out: *mut *mut mh_trace, msm_out: *mut *mut mh_trace, info: *mut mh_ec_traces_info) -> c_int;
+    pub fn mh_chunk_node_plan(bytes: *const u8, n_bytes: usize, digests: *const u8, records: *const mh_kn_record, n: usize, p2_cycles: u64, log_n: c_int, info: *mut mh_chunk_node_info) -> c_int;
+    pub fn mh_chunk_node_trace_build(ctx: *mut mh_ctx, p2: *const mh_trace, bytes: *const u8, n_bytes: usize, digests: *const u8, records: *const mh_kn_record, n: usize, log_n: c_int, out: *mut *mut mh_trace, info: *mut mh_chunk_node_info) -> c_int;
+    pub fn mh_transcript_eval_plan(nodes: *const mh_te_node, n_nodes: usize, terms: *const mh_te_term, n_terms: usize, limbs: *const u32, n_lit: usize, root: u64, p2_cycles: u64, log_n: c_int, row_start: *mut u32, info: *mut mh_transcript_eval_info) -> c_int;
+    pub fn mh_transcript_eval_trace_build(ctx: *mut mh_ctx, p2: *const mh_trace, nodes: *const mh_te_node, n_nodes: usize, terms: *const mh_te_term, n_terms: usize, limbs: *const u32, n_lit: usize, root: u64, log_n: c_int, out: *mut *mut mh_trace, root_felts: *mut u64, info: *mut mh_transcript_eval_info) -> c_int;
 }

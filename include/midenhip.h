@@ -1564,6 +1564,113 @@ int mh_ec_traces_build(mh_ctx* ctx, const mh_ec_group* groups, size_t n_groups, 
                        mh_trace** groups_out /* width 6 */, mh_trace** points_out /* width 14 */, mh_trace** add_out /* width 21 */,
                        mh_trace** msm_out /* width 38 */, mh_ec_traces_info* info /* may be NULL */);
 
+/* ---- the precompile prover's ChunkNode and TranscriptEval traces, built on the device from the ledgers and the Poseidon2 trace ----
+ * mh_chunk_node_trace_build returns the main trace of ChunkNodeAir (42 columns, index 0 of mh_prove_precompile_traces,
+ * mh_check_precompile_traces and mh_fill_multiplicities_precompile_traces), mh_transcript_eval_trace_build that of TranscriptEvalAir (39
+ * columns, index 5), device-resident.  Both read their digests from `p2`, the device-resident Poseidon2 chiplet trace (width 32) that
+ * mh_poseidon2_chiplet_trace_build returned on the same context: "the digest on cycle c" is its cells (row 16 c + 15, columns 4..7), read
+ * on the context's stream behind the kernels that wrote them.  No permutation runs on the host and no digest is copied there.  Device
+ * stage: csrc/transcript_traces.hip (row bodies: csrc/transcript_traces_rows.cuh); the planners (mh_chunk_node_plan,
+ * mh_transcript_eval_plan, host only): csrc/transcript_traces_plan.cpp.  The rule is the reference's (hash/chunk/trace.rs:133-175,
+ * hash/keccak/node/trace.rs:52-113, hash/chunk_node/trace.rs:24-45, transcript/eval/trace.rs:895-1155) and is fixed.
+ *
+ * ChunkNode.  One mh_kn_record per distinct hashed input, in ledger order (KeccakNodeRequires.records, 1:1 with ChunkRequires.records):
+ * the message is bytes[offset .. offset + len), digests[i] its Keccak-256 digest (as mh_keccak_traces_build returns them), chunk_head
+ * the first row of its chunk chain, sponge_head its first sponge row, perm_chunks the first cycle of the chain's absorption,
+ * perm_digest_chunks / perm_keccak the one-block absorptions of the digest and of the node, out_mult the node's readers.
+ *   chunk     columns 0..11.  n_chunks = max(1, ceil(len / 32)); row chunk_head + c = row, perm_chunks + c, 1, c == 0, and the eight
+ *             little-endian u32 felts of message bytes 32 c .. 32 c + 31, zero-padded.  Dead rows: row, next_perm, 0, ..., next_perm
+ *             running on from the LAST record's perm_chunks + n_chunks (from 0 without records).
+ *   node      columns 12..41.  Row i = 1, sponge_head, len / 136 + 1, chunk_head, n_chunks, perm_chunks, len, perm_digest_chunks,
+ *             perm_keccak, the digest as eight little-endian u32 felts, the digests on cycles perm_chunks + n_chunks - 1,
+ *             perm_digest_chunks and perm_keccak, out_mult mod p.  Rows below are zero.
+ *   height    max(2, next_pow2(n), next_pow2(total chunks)).  log_n = -1 takes it; a larger one pads; a smaller one is refused.
+ *   refusals  MH_ERR_INVALID, *out untouched, nothing allocated, `info` filled, mh_last_error names kind, index and operand; the lowest
+ *             kind first, within it the lowest index.  The planner's: 1 a NULL pointer where one is required (operand 0 bytes, 1 digests,
+ *             2 records, 3 p2 -- or a p2 of another context or width --, 4 out); 2 offset + len past n_bytes (index: the record); 3 a
+ *             chunk_head that is not the running sum of n_chunks; 4 a sponge_head that is not a multiple of 32; 5 a cycle at or beyond
+ *             the cycles of p2 (operand 0 the chain's last, 1 perm_digest_chunks, 2 perm_keccak); 6 more than 2^24 rows (index: the
+ *             rows) or a log_n above 24 (index: the log); 7 log_n below the height needed (index: the rows needed).  The device's, one
+ *             packed 64-bit minimum read back once before the trace is allocated: 8 a chain that is not one absorption of p2 --
+ *             is_absorb (column 3) is not 0 on cycle perm_chunks (operand 0) or not 1 on one of the n_chunks - 1 cycles behind it
+ *             (operand 1); 9 a digest cycle that does not end an absorption -- is_absorb is not 0 on the cycle behind it, where there is
+ *             one, or the cycle is padding (all zero) -- (operand 0 the chain's last cycle, 1 perm_digest_chunks, 2 perm_keccak).
+ *
+ * TranscriptEval.  The transcript DAG as mh_te_node records in recording order (children before parents), the MSM claims' term rows
+ * (mh_te_term: the node indices of base and scalar) and a pool of 256-bit literals, limbs[n_lit][8] little-endian u32.
+ *   kinds     0 ZERO, 1 AND, 2 UINT_LEAF, 3 UINT_PIN, 4 UINT_OP (op 1 add, 2 sub, 3 mul, 4 is), 5 EC_CREATE, 6 EC_PAI, 7 EC_OP (op 1 add,
+ *             2 sub, 3 is), 8 EC_MSM.  Truthy: ZERO, AND, UINT_PIN and the two `is`; uint values: UINT_LEAF and the other UINT_OPs; EC
+ *             values: EC_CREATE, EC_PAI, the other EC_OPs, EC_MSM.
+ *   fields    lhs, rhs: the operands -- a node index below the record's own, or (AND only) -1 - c: an external True binding, the digest
+ *             on cycle c of p2 (a Keccak claim's h_keccak).  A leaf's or pin's lhs indexes the literal pool (lo = limbs 0..3, hi = 4..7);
+ *             an MSM's lhs, rhs are term_start, n_terms.  perm: the node's own first cycle (ignored for ZERO).  ptr: the stored uint /
+ *             point the node stands for (an op's result, 0 for `is`; an MSM's value point).  bound_ptr: the modulus row of a uint node,
+ *             of a created point's coordinates, an MSM's scalar bound.  group: EC_CREATE, EC_PAI, EC_OP (0 for `is`), EC_MSM.  expr: the
+ *             MSM chiplet's expression.  Fields a kind does not name are ignored.
+ *   derived   h = the digest on cycle perm (MSM row idx: perm + idx; ZERO: zeros).  The lhs / rhs hashes = the operand's h (an MSM
+ *             operand's: the digest on its last cycle).  a_ptr, b_ptr (an MSM row's base_ptr, scalar_ptr) = the operands' ptr.  out_mult
+ *             of a value node = its readers, counted on the device: uses as an operand of UINT_OP / EC_CREATE / EC_OP and as an MSM
+ *             term, a == b counting twice.  out_mult of the root is 0, of every other truthy node 1.  Tag arguments and flags as the
+ *             reference lays them.
+ *   rows      row 0 the root; then every other non-ZERO node in list order, an MSM on n_terms rows (head / last flags, msm_idx, ptr and
+ *             out_mult on the last row only); then ONE merged ZERO row whose out_mult is the number of ZERO nodes other than the root,
+ *             if there are any; then zero rows.  height = max(2, next_pow2(active rows)).
+ *   refusals  as above.  The planner's: 1 a NULL pointer (operand 0 nodes, 1 terms, 2 limbs, 3 p2, 4 out); 2 an unknown kind (operand
+ *             0) or an op outside the kind's range (operand 1); 3 a source that is out of range or not below the own index (operand 0
+ *             lhs, 1 rhs; a negative source anywhere but under an AND; a literal index >= n_lit: operand 0; an MSM with term_start +
+ *             n_terms past the term rows: operand 0, with n_terms = 0: operand 1), or a term node that is (index: the term row, operand 2
+ *             base, 3 scalar); 4 a root index out of range or a root that is not of a truthy kind (index: the root); 5 a cycle at or
+ *             beyond the cycles of p2 (operand 0 the node's own, an MSM's last; 1 an external lhs; 2 an external rhs); 6 more than 2^24
+ *             rows (or 2^25 nodes) or a log_n above 24; 7 log_n too small (index: the rows needed).  The device's checking pass: 8 an operand of the
+ *             wrong class -- a value under an AND, a truthy or EC node under a uint op or a create, a uint node under an EC op (operand 0
+ *             lhs, 1 rhs), as an MSM base or an EC node as an MSM scalar (index: the term row, operand 2 base, 3 scalar); 9 operands
+ *             under different moduli: an operand's bound_ptr of a UINT_OP / EC_CREATE against the record's (operand 0 lhs, 1 rhs), an
+ *             MSM scalar's against the record's (index: the term row, operand 3); 10 an `is` over distinct pointers; 11 a truthy node
+ *             that is never read (operand 0: a stray unasserted claim) or read twice (operand 1: Truthy consumed twice), or the root
+ *             read at all (operand 2); 12 a value node nobody reads; 13 a perm that is not a one-block absorption of p2 (operand 0 it
+ *             continues one, 1 it does not end there); 14 an MSM span that is not one absorption of n_terms blocks (operand 0 its first
+ *             cycle continues one; 1 a later cycle does not, index: the term row; 2 it does not end on its last); 15 an external cycle
+ *             that does not end an absorption (operand 0 lhs, 1 rhs).
+ *   result    root_felts (may be NULL): the four felts of row 0's h, the statement's public input -- the call's one read-back besides
+ *             the minimum.
+ * No VALUE is checked: that a cycle's capacity and rate are the node's tag and operands is the AIR's bus, which mh_check_balance* finds.
+ * Every cell of both traces is written by one lane, padding included; the counters and the minimum are scratch the calls clear
+ * themselves; a second call leaves the same bytes.
+ * Not in scope: recording the transcript (deduplication, interning: the host's); counting the Poseidon2 in_mult / out_mult; chunk
+ * chains laid by anything but a Keccak node; device-resident input lists; sharded contexts; more than 2^24 rows. */
+typedef struct mh_kn_record { uint64_t offset, len, chunk_head, sponge_head, perm_chunks, perm_digest_chunks, perm_keccak, out_mult; } mh_kn_record; /* 64 bytes */
+typedef struct mh_chunk_node_info {
+  uint64_t n_records, n_chunks, p2_cycles;
+  uint64_t rows_needed, rows;   /* the least height, and the one taken */
+  int32_t defect_kind;          /* 0 none */
+  int32_t defect_operand;
+  uint64_t defect_index;
+} mh_chunk_node_info;           /* 56 bytes */
+typedef struct mh_te_node { uint32_t kind, op; int64_t lhs, rhs; uint64_t perm, ptr, bound_ptr, group, expr; } mh_te_node;            /* 64 bytes */
+typedef struct mh_te_term { uint32_t base_node, scalar_node; } mh_te_term;                                                          /* 8 bytes */
+typedef struct mh_transcript_eval_info {
+  uint64_t n_nodes, n_terms, n_lit, p2_cycles;
+  uint64_t active_rows, n_zero; /* the rows that are not padding; the ZERO nodes other than the root */
+  uint64_t rows_needed, rows;
+  int32_t defect_kind;
+  int32_t defect_operand;
+  uint64_t defect_index;
+} mh_transcript_eval_info;      /* 80 bytes */
+/* Host only: kinds 1..7 (no pointer but `records` is read through) and the height. */
+int mh_chunk_node_plan(const uint8_t* bytes, size_t n_bytes, const uint8_t* digests, const mh_kn_record* records, size_t n,
+                       uint64_t p2_cycles, int log_n /* -1: least */, mh_chunk_node_info* info);
+int mh_chunk_node_trace_build(mh_ctx* ctx, const mh_trace* p2 /* width 32 */, const uint8_t* bytes, size_t n_bytes,
+                              const uint8_t* digests /* [n][32] */, const mh_kn_record* records, size_t n, int log_n /* -1: least */,
+                              mh_trace** out /* width 42 */, mh_chunk_node_info* info /* may be NULL */);
+/* Host only: kinds 1..7, the height and every node's first row (`limbs` is not read through). */
+int mh_transcript_eval_plan(const mh_te_node* nodes, size_t n_nodes, const mh_te_term* terms, size_t n_terms, const uint32_t* limbs,
+                            size_t n_lit, uint64_t root, uint64_t p2_cycles, int log_n /* -1: least */,
+                            uint32_t* row_start /* [n_nodes] or NULL */, mh_transcript_eval_info* info);
+int mh_transcript_eval_trace_build(mh_ctx* ctx, const mh_trace* p2 /* width 32 */, const mh_te_node* nodes, size_t n_nodes,
+                                   const mh_te_term* terms, size_t n_terms, const uint32_t* limbs /* [n_lit][8] */, size_t n_lit,
+                                   uint64_t root, int log_n /* -1: least */, mh_trace** out /* width 39 */,
+                                   uint64_t* root_felts /* [4] or NULL */, mh_transcript_eval_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

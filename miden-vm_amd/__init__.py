@@ -48,6 +48,7 @@ EXPORTS = [
     "mh_keccak_round_program", "mh_keccak_round_levels", "mh_keccak_round_trace_build", "mh_keccak_traces_build",
     "mh_poseidon2_chiplet_plan", "mh_poseidon2_chiplet_trace_build", "mh_uint_traces_plan", "mh_uint_traces_build",
     "mh_ec_traces_plan", "mh_ec_traces_build",
+    "mh_chunk_node_plan", "mh_chunk_node_trace_build", "mh_transcript_eval_plan", "mh_transcript_eval_trace_build",
     "mh_ctx_set_salt", "mh_ctx_get_salt", "mh_tree_salt_elems", "mh_tree_salt_index", "mh_tree_download_salt", "mh_verify_hiding",
     "mh_commit_host", "mh_precompile_setup_root",
     "mh_pcs_point_ok", "mh_pcs_begin", "mh_pcs_free", "mh_pcs_shape", "mh_pcs_evals", "mh_pcs_deep", "mh_pcs_download_deep", "mh_pcs_fri_commit",
@@ -869,6 +870,121 @@ def ec_traces(ctx, groups, points, adds, exprs, terms, log_groups=-1, log_points
     return tuple(Trace.from_handle(ctx, h, int(n).bit_length() - 1, w) for h, n, w in zip(hs, rows, (6, 14, 21, 38))), info
 
 
+# ---- the precompile prover's ChunkNode and TranscriptEval traces (include/midenhip.h mh_chunk_node_*, mh_transcript_eval_*) ----
+KN_RECORD_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u8"), ("chunk_head", "<u8"), ("sponge_head", "<u8"), ("perm_chunks", "<u8"),
+                            ("perm_digest_chunks", "<u8"), ("perm_keccak", "<u8"), ("out_mult", "<u8")])                                      # mh_kn_record
+TE_NODE_DTYPE = np.dtype([("kind", "<u4"), ("op", "<u4"), ("lhs", "<i8"), ("rhs", "<i8"), ("perm", "<u8"), ("ptr", "<u8"), ("bound_ptr", "<u8"),
+                          ("group", "<u8"), ("expr", "<u8")])                                                                                  # mh_te_node
+TE_TERM_DTYPE = np.dtype([("base_node", "<u4"), ("scalar_node", "<u4")])                                                                       # mh_te_term
+TE_ZERO, TE_AND, TE_UINT_LEAF, TE_UINT_PIN, TE_UINT_OP, TE_EC_CREATE, TE_EC_PAI, TE_EC_OP, TE_EC_MSM = range(9)                                # mh_te_node.kind
+
+
+class ChunkNodeInfo(C.Structure):
+    """mh_chunk_node_info: the records, the chunk rows, the cycles of p2, the least height and the one taken; `defect_kind` 0 none, 1..7 the
+    planner's (a NULL pointer or a p2 of another context or width; offset + len past n_bytes; chunk_head not the running sum; sponge_head
+    not a multiple of 32; a cycle beyond p2; more than 2^24 rows or a log above 24; log below the height, index the rows needed), 8, 9 the
+    device's (a chain that is not one absorption of p2; a digest cycle that does not end one)."""
+    _fields_ = [("n_records", C.c_uint64), ("n_chunks", C.c_uint64), ("p2_cycles", C.c_uint64), ("rows_needed", C.c_uint64), ("rows", C.c_uint64),
+                ("defect_kind", C.c_int32), ("defect_operand", C.c_int32), ("defect_index", C.c_uint64)]
+
+    def __repr__(self):
+        return "ChunkNodeInfo(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
+class TranscriptEvalInfo(C.Structure):
+    """mh_transcript_eval_info: the lists' sizes, the cycles of p2, the active rows, the ZERO nodes other than the root, the least height
+    and the one taken; `defect_kind` 0 none, 1..7 the planner's (a NULL pointer or a p2 of another context or width; an unknown kind or
+    op; a source, literal, term span or term node out of range; a root out of range or not truthy; a cycle beyond p2; more than 2^24 rows
+    or a log above 24; log below the height, index the rows needed), 8..15 the device's (an operand of the wrong class; different moduli;
+    an `is` over distinct pointers; a truthy node not read once or the root read; a value node nobody reads; a perm that is not a
+    one-block absorption; an MSM span that is not one absorption; an external cycle that does not end one)."""
+    _fields_ = [("n_nodes", C.c_uint64), ("n_terms", C.c_uint64), ("n_lit", C.c_uint64), ("p2_cycles", C.c_uint64), ("active_rows", C.c_uint64),
+                ("n_zero", C.c_uint64), ("rows_needed", C.c_uint64), ("rows", C.c_uint64), ("defect_kind", C.c_int32), ("defect_operand", C.c_int32),
+                ("defect_index", C.c_uint64)]
+
+    def __repr__(self):
+        return "TranscriptEvalInfo(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
+def _plan_refused(entry, info):
+    e = MidenHipError(f"{entry}: defect {info.defect_kind}, index {info.defect_index}, operand {info.defect_operand}")
+    e.info = info
+    return e
+
+
+def _cn_call_args(data, digests, records):
+    d = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data, dtype=np.uint8).reshape(-1)
+    g = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+    r = _records(records, KN_RECORD_DTYPE)
+    if g.shape[0] != r.size:
+        raise MidenHipError("chunk_node: one 32-byte digest per record expected")
+    return (d, g, r), [_void_p(d), d.size, _void_p(g), _void_p(r), r.size]
+
+
+def chunk_node_plan(data, digests, records, p2_cycles, log_n=-1, lib=None):
+    """mh_chunk_node_plan (host only): validates the records against the bytes and the cycles of the Poseidon2 trace and gives the height
+    -> ChunkNodeInfo.  A defect raises MidenHipError with `e.info`."""
+    lib = lib or load_library()
+    keep, args = _cn_call_args(data, digests, records)
+    info = ChunkNodeInfo()
+    lib.mh_chunk_node_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(ChunkNodeInfo)]
+    if lib.mh_chunk_node_plan(*args, int(p2_cycles), -1 if log_n is None else int(log_n), C.byref(info)) != 0:
+        raise _plan_refused("mh_chunk_node_plan", info)
+    return info
+
+
+def chunk_node_trace(ctx, p2, data, digests, records, log_n=-1):
+    """mh_chunk_node_trace_build: ChunkNodeAir's main trace on the device -- `p2` the device-resident Poseidon2 chiplet Trace
+    (poseidon2_chiplet_trace on this context), `data` the message bytes, `digests` uint8 [n, 32] (keccak_traces' digests), `records`
+    KN_RECORD_DTYPE (offset, len, chunk_head, sponge_head, perm_chunks, perm_digest_chunks, perm_keccak, out_mult), one per distinct
+    hashed input -> (Trace [., 42], ChunkNodeInfo).  The three digests of a node row are read from `p2` on the device.  log_n -1 (or
+    None): the least height.  A refusal raises MidenHipError with `e.info` (kind, index, operand)."""
+    keep, args = _cn_call_args(data, digests, records)
+    lib = ctx.lib
+    lib.mh_chunk_node_trace_build.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                              C.POINTER(C.c_void_p), C.POINTER(ChunkNodeInfo)]
+    h, info = C.c_void_p(), ChunkNodeInfo()
+    rc = lib.mh_chunk_node_trace_build(ctx.h, p2.h, *args, -1 if log_n is None else int(log_n), C.byref(h), C.byref(info))
+    _mem_section_result(lib, ctx, rc, info)
+    return Trace.from_handle(ctx, h, int(info.rows).bit_length() - 1, 42), info
+
+
+def _te_call_args(nodes, terms, limbs, root):
+    n, t = _records(nodes, TE_NODE_DTYPE), _records(terms, TE_TERM_DTYPE)
+    lit = np.ascontiguousarray(limbs, dtype=np.uint32).reshape(-1, 8)
+    return (n, t, lit), [_void_p(n), n.size, _void_p(t), t.size, _void_p(lit), lit.shape[0], int(root)]
+
+
+def transcript_eval_plan(nodes, terms, limbs, root, p2_cycles, log_n=-1, lib=None):
+    """mh_transcript_eval_plan (host only): validates kinds, sources and cycles and gives the height and every node's first row
+    -> (row_start uint32 [n_nodes], TranscriptEvalInfo).  A defect raises MidenHipError with `e.info`."""
+    lib = lib or load_library()
+    keep, args = _te_call_args(nodes, terms, limbs, root)
+    row_start, info = np.zeros(keep[0].size, dtype=np.uint32), TranscriptEvalInfo()
+    lib.mh_transcript_eval_plan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_int,
+                                            C.c_void_p, C.POINTER(TranscriptEvalInfo)]
+    if lib.mh_transcript_eval_plan(*args, int(p2_cycles), -1 if log_n is None else int(log_n), _void_p(row_start), C.byref(info)) != 0:
+        raise _plan_refused("mh_transcript_eval_plan", info)
+    return row_start, info
+
+
+def transcript_eval_trace(ctx, p2, nodes, terms, limbs, root, log_n=-1, want_root=True):
+    """mh_transcript_eval_trace_build: TranscriptEvalAir's main trace on the device -- `p2` the device-resident Poseidon2 chiplet Trace,
+    `nodes` TE_NODE_DTYPE (kind TE_ZERO .. TE_EC_MSM, op, lhs, rhs, perm, ptr, bound_ptr, group, expr) in recording order, `terms`
+    TE_TERM_DTYPE (the MSM claims' (base, scalar) node indices), `limbs` uint32 [n_lit, 8] the literal pool, `root` the root's node index
+    -> (Trace [., 39], TranscriptEvalInfo, the public root as four ints or None).  Every hash is read from `p2` on the device; value
+    nodes' out_mult is counted there.  A refusal raises MidenHipError with `e.info` (kind, index, operand)."""
+    keep, args = _te_call_args(nodes, terms, limbs, root)
+    lib = ctx.lib
+    lib.mh_transcript_eval_trace_build.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                   C.c_uint64, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(TranscriptEvalInfo)]
+    h, info, felts = C.c_void_p(), TranscriptEvalInfo(), np.zeros(4, dtype=np.uint64)
+    rc = lib.mh_transcript_eval_trace_build(ctx.h, p2.h, *args, -1 if log_n is None else int(log_n), C.byref(h),
+                                            felts.ctypes.data_as(C.c_void_p) if want_root else None, C.byref(info))
+    _mem_section_result(lib, ctx, rc, info)
+    return Trace.from_handle(ctx, h, int(info.rows).bit_length() - 1, 39), info, ([int(x) for x in felts] if want_root else None)
+
+
 def load_library():
     """dlopen libmidenhip.so (does not touch the GPU)."""
     global _lib
@@ -969,6 +1085,14 @@ class Ctx:
     def ec_traces(self, groups, points, adds, exprs, terms, log_groups=-1, log_points=-1, log_add=-1, log_msm=-1):
         """ec_traces on this context: the session's traces 8..11 (EcGroups, EcPointStore, EcGroupAdd, EcMsm) from the EC ledgers."""
         return ec_traces(self, groups, points, adds, exprs, terms, log_groups, log_points, log_add, log_msm)
+
+    def chunk_node_trace(self, p2, data, digests, records, log_n=-1):
+        """chunk_node_trace on this context: the session's trace 0 (ChunkNode) from the node records and the Poseidon2 Trace."""
+        return chunk_node_trace(self, p2, data, digests, records, log_n)
+
+    def transcript_eval_trace(self, p2, nodes, terms, limbs, root, log_n=-1, want_root=True):
+        """transcript_eval_trace on this context: the session's trace 5 (TranscriptEval) from the transcript's nodes and the Poseidon2 Trace."""
+        return transcript_eval_trace(self, p2, nodes, terms, limbs, root, log_n, want_root)
 
     # ---- profiler ----
     def prof_enable(self, on=True):
@@ -2424,6 +2548,15 @@ class Precompile:
     def ec_traces(self, groups, points, adds, exprs, terms, log_groups=-1, log_points=-1, log_add=-1, log_msm=-1):
         """ec_traces on this object's context: the session's traces 8..11 (EcGroups, EcPointStore, EcGroupAdd, EcMsm) from the EC ledgers."""
         return ec_traces(self.ctx, groups, points, adds, exprs, terms, log_groups, log_points, log_add, log_msm)
+
+    def chunk_node_trace(self, p2, data, digests, records, log_n=-1):
+        """chunk_node_trace on this object's context: the session's trace 0 (ChunkNode) from the node records and the Poseidon2 Trace."""
+        return chunk_node_trace(self.ctx, p2, data, digests, records, log_n)
+
+    def transcript_eval_trace(self, p2, nodes, terms, limbs, root, log_n=-1, want_root=True):
+        """transcript_eval_trace on this object's context: the session's trace 5 (TranscriptEval) from the transcript's nodes and the
+        Poseidon2 Trace."""
+        return transcript_eval_trace(self.ctx, p2, nodes, terms, limbs, root, log_n, want_root)
 
     def keccak_traces(self, messages, chunk_heads, log_round=None, log_sponge=None, want_digests=False):
         """keccak_traces on this object's context: the session's traces 2 (Keccak round) and 4 (Keccak sponge) from the messages."""

@@ -632,6 +632,22 @@ def keccak_node_trace(requires, min_height=0):
     return t
 
 
+def chunk_node_lists(chunk_requires, node_requires):
+    """The ledgers as mh_chunk_node_trace_build takes them -> (data uint8: the distinct hashed inputs back to back, digests uint8 [n, 32],
+    records KN_RECORD_DTYPE), one record per distinct input in ledger order (`KeccakNodeRequires.records` and `ChunkRequires.records` are
+    1:1 in a `Session`)."""
+    from .. import KN_RECORD_DTYPE
+    inputs = list(node_requires.by_input)                               # insertion order = record order
+    assert len(inputs) == len(node_requires.records) == len(chunk_requires.records), "a chunk chain laid by something else than a Keccak node"
+    rec, at = np.zeros(len(inputs), dtype=KN_RECORD_DTYPE), 0
+    for i, (data, r, (_chunks, head, perm_start)) in enumerate(zip(inputs, node_requires.records, chunk_requires.records)):
+        assert node_requires.by_input[data] == i and (head, perm_start) == (r["chunk_head"], r["perm_chunks"])
+        rec[i] = (at, len(data), r["chunk_head"], r["sponge_head"], r["perm_chunks"], r["perm_digest_chunks"], r["perm_keccak"], r["out_mult"])
+        at += len(data)
+    digests = np.frombuffer(b"".join(r["keccak_digest"] for r in node_requires.records), dtype=np.uint8).reshape(-1, 32)
+    return np.frombuffer(b"".join(inputs), dtype=np.uint8), digests, rec
+
+
 def binding_requests(node_requires):
     """The transcript's readers of the nodes' truth bindings: `Binding(H_keccak, True, 0, 0)` consumed once per `require` of that input --
     the only side of the Keccak hashing stack that is still a stand-in.  -> [(bus, multiplicity, fields)] for `requirer_air(payload=7)`."""
@@ -1702,6 +1718,63 @@ def transcript_eval_trace(requires, root, min_height=0):
             row[[TE_COL_IS_EC_OP, op_col[n["op"]], TE_COL_PTR, TE_COL_A_PTR, TE_COL_B_PTR, TE_COL_TAG_ARG0, TE_COL_EC_GROUP_PTR]] = \
                 [1, 1, n["r_ptr"], n["p_ptr"], n["q_ptr"], EC_OP_IDS[n["op"]], n["group"]]
     return t, [int(x) for x in t[0, TE_COL_H:TE_COL_H + 4]]
+
+
+def transcript_lists(requires, root):
+    """The transcript as mh_transcript_eval_trace_build takes it -> (nodes TE_NODE_DTYPE in recording order, terms TE_TERM_DTYPE, limbs
+    uint32 [n_lit, 8], the root's node index).  The ledger keeps its operands as hashes and pointers; here they become node indices: a
+    value operand is the node of that hash AND pointer (equal values at two pointers are two leaves with one hash), a truthy operand the
+    earliest unconsumed node of that hash (every ZERO leaf hashes to zeros), and a hash no node has is an issued handle (`issue`: a Keccak
+    claim's h_keccak): -1 - the last cycle of the absorption with that digest, found among the digests the Poseidon2 ledger already
+    holds -- nothing is hashed here."""
+    from .. import (TE_NODE_DTYPE, TE_TERM_DTYPE, TE_ZERO, TE_AND, TE_UINT_LEAF, TE_UINT_PIN, TE_UINT_OP, TE_EC_CREATE, TE_EC_PAI, TE_EC_OP,
+                    TE_EC_MSM)
+    p2 = requires.p2
+    external = {}
+    for idx, d in p2._digests.items():
+        start, n = p2.span(idx)
+        external.setdefault(tuple(int(x) for x in d), -1 - (start + n - 1))
+    uints, points, truthies = {}, {}, {}                                # (hash, ptr) -> node | (hash, point) -> node | hash -> [unconsumed nodes]
+    nodes, terms, limbs, index_of = np.zeros(len(requires.nodes), dtype=TE_NODE_DTYPE), [], [], {}
+
+    def truthy(hash_):
+        waiting = truthies.get(tuple(hash_))
+        return waiting.pop(0) if waiting else external[tuple(int(x) for x in hash_)]
+    for i, n in enumerate(requires.nodes):
+        index_of[n["id"]], kind, hash_ = i, n["kind"], tuple(n["hash"])
+        rec = dict(kind=TE_ZERO, op=0, lhs=0, rhs=0, perm=n["perm"] or 0, ptr=0, bound_ptr=0, group=0, expr=0)
+        if kind == "and":
+            rec.update(kind=TE_AND, lhs=truthy(n["lhs"]), rhs=truthy(n["rhs"]))
+        elif kind == "uint_leaf":
+            limbs.append(list(n["lo"]) + list(n["hi"]))
+            rec.update(kind=TE_UINT_PIN if n["pinned"] else TE_UINT_LEAF, lhs=len(limbs) - 1, ptr=n["ptr"], bound_ptr=n["bound_ptr"])
+        elif kind == "uint_op":
+            rec.update(kind=TE_UINT_OP, op=UINT_OP_IDS[n["op"]], lhs=uints[tuple(n["lhs"]), n["a_ptr"]], rhs=uints[tuple(n["rhs"]), n["b_ptr"]],
+                       ptr=n["r_ptr"], bound_ptr=n["bound_ptr"])
+        elif kind == "ec_create" and n["is_pai"]:
+            rec.update(kind=TE_EC_PAI, ptr=n["point"], group=n["group"])
+        elif kind == "ec_create":
+            rec.update(kind=TE_EC_CREATE, lhs=uints[tuple(n["lhs"]), n["x_ptr"]], rhs=uints[tuple(n["rhs"]), n["y_ptr"]], ptr=n["point"],
+                       bound_ptr=n["bound_ptr"], group=n["group"])
+        elif kind == "ec_op":
+            rec.update(kind=TE_EC_OP, op=EC_OP_IDS[n["op"]], lhs=points[tuple(n["lhs"]), n["p_ptr"]], rhs=points[tuple(n["rhs"]), n["q_ptr"]],
+                       ptr=n["r_ptr"], group=n["group"])
+        elif kind == "ec_msm":
+            rec.update(kind=TE_EC_MSM, lhs=len(terms), rhs=len(n["absorbs"]), perm=n["absorbs"][0]["perm"], ptr=n["val"], bound_ptr=n["bound"],
+                       group=n["group"], expr=n["expr"])
+            terms += [(points[tuple(a["base_hash"]), a["base_ptr"]], uints[tuple(a["scalar_hash"]), a["scalar_ptr"]]) for a in n["absorbs"]]
+        else:
+            assert kind == "zero", kind
+        nodes[i] = tuple(rec[f] for f in TE_NODE_DTYPE.names)
+        is_truthy = kind in ("zero", "and") or (kind == "uint_leaf" and n["pinned"]) or (kind in ("uint_op", "ec_op") and n["op"] == "is")
+        if is_truthy:
+            truthies.setdefault(hash_, []).append(i)
+        elif kind in ("uint_leaf", "uint_op"):
+            uints[hash_, n["r_ptr"] if kind == "uint_op" else n["ptr"]] = i
+        else:
+            points[hash_, n["val"] if kind == "ec_msm" else n["r_ptr"] if kind == "ec_op" else n["point"]] = i
+    assert root["id"] in index_of, "the root must be a recorded node (zero leaf, AND, Is or pin), not a raw handle"
+    return (nodes, np.array(terms, dtype=TE_TERM_DTYPE).reshape(-1), np.array(limbs, dtype=np.uint32).reshape(-1, 8), index_of[root["id"]])
 
 
 def k1_multiples(n):
