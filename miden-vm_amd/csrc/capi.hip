@@ -309,9 +309,7 @@ int mh_trace_from_device(mh_ctx* c, const uint64_t* device_rowmajor, int log_n, 
   MH_REQUIRE(hipPointerGetAttributes(&attr, device_rowmajor) == hipSuccess && attr.type == hipMemoryTypeDevice,
              "mh_trace_from_device needs a device pointer (use mh_trace_upload for host memory)");
   const size_t n = (size_t)1 << log_n;
-  std::unique_ptr<mh_trace> t(new mh_trace());
-  t->ctx = c; t->log_n = log_n; t->width = width;
-  t->cols.alloc(n * width * 8);
+  std::unique_ptr<mh_trace> t = trace_new(c, log_n, width);
   launch_transpose_rm_to_cm(c, device_rowmajor, t->cols.u(), n, width);
   c->sync();
   *out = t.release();

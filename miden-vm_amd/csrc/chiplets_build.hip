@@ -105,9 +105,7 @@ extern "C" int mh_miden_chiplets_build(mh_ctx* c, const mh_chiplets_lists* l, in
       throw MhError(MH_ERR_INVALID, buf);
     }
     const u64 height = (u64)1 << log_n;
-    std::unique_ptr<mh_trace> t(new mh_trace());
-    t->ctx = c; t->log_n = log_n; t->width = SEC_CHIPLETS_WIDTH;
-    t->cols.alloc(height * SEC_CHIPLETS_WIDTH * 8);
+    std::unique_ptr<mh_trace> t = trace_new(c, log_n, SEC_CHIPLETS_WIDTH);
     HIP_CHECK(hipMemsetAsync(t->cols.p, 0, height * SEC_CHIPLETS_WIDTH * 8, c->stream));
     // a builder's refusal has filled its info and the context's error text: hand both on
     auto section = [&](int s, int rc, int defect, u64 index, u64 got_rows) {

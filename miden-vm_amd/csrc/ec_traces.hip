@@ -6,19 +6,20 @@
 // the point store, one 56-byte record per addition, one 48-byte record per expression and (base, scalar) per term row; the planner
 // (ec_traces_plan.cpp, host only) has validated what one record shows and given the heights and every expression's first term row.
 // Two stages with one read-back between them:
-//   check    k_ec_point_check  a lane per point: its read of its group.
-//            k_ec_add_check    a lane per addition: p, q, r and the group in range, the kind against which operands are points at
+//   check    ec_point_check    a lane per point: its read of its group.
+//            ec_add_check      a lane per addition: p, q, r and the group in range, the kind against which operands are points at
 //                              infinity, the mint's ordering; then its reads of p, q and, in the live cases, of r and the group.
-//            k_ec_expr_check   a lane per expression: val and group in range and consistent, an intro's base; its reads of the group,
+//            ec_expr_check     a lane per expression: val and group in range and consistent, an intro's base; its reads of the group,
 //                              of its operands and (neg) of the two value points.
-//            k_ec_term_check   a lane per term row: its expression by a search over the first rows, the bases' order, and for a combine
+//            ec_term_check     a lane per term row: its expression by a search over the first rows, the bases' order, and for a combine
 //                              the merge: this row's cursors (two binary searches) advanced by its takes against the next row's.
 //            The counters are integers added once per wave where the lanes agree (wave_count.cuh): in a session every point and every
 //            live addition reads ONE group.  Defects (kinds 8..15) go into one packed 64-bit minimum: kind, section, index, operand.
-//   rows     after the minimum has been read back clean and the traces are allocated: k_ec_groups_rows, k_ec_points_rows,
-//            k_ec_add_rows (four roles per block) and k_ec_msm_rows, a lane per trace row, padding included.  Consecutive lanes hold
+//   rows     after the minimum has been read back clean and the traces are allocated: ec_groups_row, ec_points_row,
+//            ec_add_row (four roles per block) and ec_msm_row, a lane per trace row, padding included.  Consecutive lanes hold
 //            consecutive rows of a column-major column: every store is a whole line.
-// The bodies are in ec_traces_rows.cuh.  The counters and the minimum are scratch that the call clears itself; every cell of the four
+// The bodies named above are in ec_traces_rows.cuh; their kernels are ledger_stage.cuh's lane_per_record<body> and lane_per_row<body>, as
+// the defect word, its read-back and the refusal's message are.  The counters and the minimum are scratch that the call clears itself; every cell of the four
 // traces has exactly one writer: a second call leaves the same bytes.  No LDS, no scratch memory.
 #include "section_out.cuh"
 #include "ec_traces_rows.cuh"
@@ -33,49 +34,6 @@ static_assert(sizeof(mh_ec_traces_info) == 128, "mh_ec_traces_info is 128 bytes"
 
 namespace {
 constexpr int EC_BT = 256;
-}
-
-__global__ __launch_bounds__(EC_BT) void k_ec_point_check(EcLists L) {
-  const u32 i = blockIdx.x * EC_BT + threadIdx.x;
-  if (i < L.n_points) ec_point_check(L, i);
-}
-
-__global__ __launch_bounds__(EC_BT) void k_ec_add_check(EcLists L) {
-  const u32 i = blockIdx.x * EC_BT + threadIdx.x;
-  if (i < L.n_add) ec_add_check(L, i);
-}
-
-__global__ __launch_bounds__(EC_BT) void k_ec_expr_check(EcLists L) {
-  const u32 i = blockIdx.x * EC_BT + threadIdx.x;
-  if (i < L.n_exprs) ec_expr_check(L, i);
-}
-
-__global__ __launch_bounds__(EC_BT) void k_ec_term_check(EcLists L) {
-  const u32 i = blockIdx.x * EC_BT + threadIdx.x;
-  if (i < L.n_terms) ec_term_check(L, i);
-}
-
-__global__ __launch_bounds__(EC_BT) void k_ec_groups_rows(EcLists L, u64 n, u64* __restrict__ out) {
-  const u64 t = (u64)blockIdx.x * EC_BT + threadIdx.x;
-  if (t < n) ec_groups_row(L, n, out, t);
-}
-
-__global__ __launch_bounds__(EC_BT) void k_ec_points_rows(EcLists L, u64 n, u64* __restrict__ out) {
-  const u64 t = (u64)blockIdx.x * EC_BT + threadIdx.x;
-  if (t < n) ec_points_row(L, n, out, t);
-}
-
-__global__ __launch_bounds__(EC_BT) void k_ec_add_rows(EcLists L, u64 n, u64* __restrict__ out) {
-  const u64 t = (u64)blockIdx.x * EC_BT + threadIdx.x;
-  if (t < n) ec_add_row(L, n, out, t);
-}
-
-__global__ __launch_bounds__(EC_BT) void k_ec_msm_rows(EcLists L, u64 n, u64* __restrict__ out) {
-  const u64 t = (u64)blockIdx.x * EC_BT + threadIdx.x;
-  if (t < n) ec_msm_row(L, n, out, t);
-}
-
-namespace {
 const char* const EC_WHAT[] = {"",
                                "a null list where a count is nonzero",
                                "more than 2^24 rows in a trace, or a log_* above 24",
@@ -94,23 +52,7 @@ const char* const EC_WHAT[] = {"",
                                "an intro whose val is not its base"};
 
 [[noreturn]] void ec_refuse(const mh_ec_traces_info* info) {
-  char buf[360];
-  snprintf(buf, sizeof buf, "mh_ec_traces_build: section %d, defect %d, index %llu, operand %d: %s", info->defect_section, info->defect_kind,
-           (unsigned long long)info->defect_index, info->defect_operand, EC_WHAT[info->defect_kind]);
-  throw MhError(MH_ERR_INVALID, buf);
-}
-
-int ec_log2(u64 rows) {
-  int l = 0;
-  while (((u64)1 << l) < rows) l++;
-  return l;
-}
-
-std::unique_ptr<mh_trace> ec_new_trace(mh_ctx* c, u64 rows, int width) {
-  std::unique_ptr<mh_trace> t(new mh_trace());
-  t->ctx = c; t->log_n = ec_log2(rows); t->width = width;
-  t->cols.alloc(rows * width * 8);
-  return t;
+  ledger_refuse("mh_ec_traces_build", {info->defect_kind, info->defect_section, info->defect_index, info->defect_operand}, EC_WHAT[info->defect_kind]);
 }
 }  // namespace
 
@@ -151,47 +93,42 @@ extern "C" int mh_ec_traces_build(mh_ctx* c, const mh_ec_group* groups, size_t n
                     count, count + n_groups, count + n_groups + n_points, (unsigned long long*)ddefect.p};
     if (n_points) {
       ProfScope ps(c, "ec_point_check", (double)n_points * sizeof(mh_ec_point));
-      MH_LAUNCH(k_ec_point_check, dim3(sec_grid(n_points, EC_BT)), dim3(EC_BT), 0, c->stream, L);
+      launch_per_record<EcLists, &EcLists::n_points, ec_point_check, EC_BT>(c, L);
     }
     if (n_add) {
       ProfScope ps(c, "ec_add_check", (double)n_add * (sizeof(mh_ec_add_op) + 3 * sizeof(mh_ec_point)));
-      MH_LAUNCH(k_ec_add_check, dim3(sec_grid(n_add, EC_BT)), dim3(EC_BT), 0, c->stream, L);
+      launch_per_record<EcLists, &EcLists::n_add, ec_add_check, EC_BT>(c, L);
     }
     if (n_exprs) {
       ProfScope ps(c, "ec_expr_check", (double)n_exprs * 3 * sizeof(mh_msm_expr));
-      MH_LAUNCH(k_ec_expr_check, dim3(sec_grid(n_exprs, EC_BT)), dim3(EC_BT), 0, c->stream, L);
+      launch_per_record<EcLists, &EcLists::n_exprs, ec_expr_check, EC_BT>(c, L);
     }
     if (n_terms) {
       ProfScope ps(c, "ec_term_check", (double)n_terms * (sizeof(mh_msm_expr) + 3 * sizeof(mh_msm_term)));
-      MH_LAUNCH(k_ec_term_check, dim3(sec_grid(n_terms, EC_BT)), dim3(EC_BT), 0, c->stream, L);
+      launch_per_record<EcLists, &EcLists::n_terms, ec_term_check, EC_BT>(c, L);
     }
-    unsigned long long defect = 0;
-    c->d2h(&defect, ddefect.p, 8);  // waits for the checking pass: nothing is allocated for the traces before it is known clean
-    if (defect != ~0ull) {
-      info->defect_kind = (int32_t)(defect >> 56);
-      info->defect_section = (int32_t)((defect >> 54) & 3);
-      info->defect_index = (defect >> 8) & 0xffffffffull;
-      info->defect_operand = (int32_t)(defect & 0xff);
-      MH_REQUIRE(info->defect_kind >= 8 && info->defect_kind <= 15, "mh_ec_traces_build: the checking pass left an unreadable defect word");
+    const LedgerDefect d = ledger_read_defect(c, ddefect.p, 8, 15, "mh_ec_traces_build", "checking");
+    if (d.kind) {
+      info->defect_kind = d.kind; info->defect_section = d.section; info->defect_index = d.index; info->defect_operand = d.operand;
       ec_refuse(info);
     }
-    std::unique_ptr<mh_trace> tg = ec_new_trace(c, info->groups_rows, EC_GROUPS_WIDTH), tp = ec_new_trace(c, info->points_rows, EC_POINTS_WIDTH),
-                              ta = ec_new_trace(c, info->add_rows, EC_ADD_WIDTH), tm = ec_new_trace(c, info->msm_rows, EC_MSM_WIDTH);
+    std::unique_ptr<mh_trace> tg = trace_new(c, ceil_log2(info->groups_rows), EC_GROUPS_WIDTH), tp = trace_new(c, ceil_log2(info->points_rows), EC_POINTS_WIDTH),
+                              ta = trace_new(c, ceil_log2(info->add_rows), EC_ADD_WIDTH), tm = trace_new(c, ceil_log2(info->msm_rows), EC_MSM_WIDTH);
     {
       ProfScope ps(c, "ec_groups_rows", 8.0 * EC_GROUPS_WIDTH * (double)info->groups_rows);
-      MH_LAUNCH(k_ec_groups_rows, dim3(sec_grid(info->groups_rows, EC_BT)), dim3(EC_BT), 0, c->stream, L, (u64)info->groups_rows, tg->cols.u());
+      launch_per_row<EcLists, ec_groups_row, EC_BT>(c, L, info->groups_rows, tg->cols.u());
     }
     {
       ProfScope ps(c, "ec_points_rows", 8.0 * EC_POINTS_WIDTH * (double)info->points_rows);
-      MH_LAUNCH(k_ec_points_rows, dim3(sec_grid(info->points_rows, EC_BT)), dim3(EC_BT), 0, c->stream, L, (u64)info->points_rows, tp->cols.u());
+      launch_per_row<EcLists, ec_points_row, EC_BT>(c, L, info->points_rows, tp->cols.u());
     }
     {
       ProfScope ps(c, "ec_add_rows", 8.0 * EC_ADD_WIDTH * (double)info->add_rows);
-      MH_LAUNCH(k_ec_add_rows, dim3(sec_grid(info->add_rows, EC_BT)), dim3(EC_BT), 0, c->stream, L, (u64)info->add_rows, ta->cols.u());
+      launch_per_row<EcLists, ec_add_row, EC_BT>(c, L, info->add_rows, ta->cols.u());
     }
     {
       ProfScope ps(c, "ec_msm_rows", 8.0 * EC_MSM_WIDTH * (double)info->msm_rows);
-      MH_LAUNCH(k_ec_msm_rows, dim3(sec_grid(info->msm_rows, EC_BT)), dim3(EC_BT), 0, c->stream, L, (u64)info->msm_rows, tm->cols.u());
+      launch_per_row<EcLists, ec_msm_row, EC_BT>(c, L, info->msm_rows, tm->cols.u());
     }
     // the lists and counters are pooled buffers: they go back to the pool when this scope ends, ordered behind the row kernels on the stream
     *groups_out = tg.release();

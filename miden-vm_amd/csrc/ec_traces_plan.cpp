@@ -10,26 +10,7 @@
 //   6 an expression kind outside 0..2, n_rows = 0, an intro of more than one row, the n_rows not summing to n_terms
 //   7 an operand that is 0 or not an earlier expression, or nonzero where the kind has none
 // Whatever dereferences another record (kinds 8..15) is the device pass's to judge.
-#include "../../include/midenhip.h"
-#include <vector>
-
-namespace {
-constexpr uint64_t EC_MAX_ROWS = (uint64_t)1 << 24;
-
-int ec_defect(mh_ec_traces_info* info, int section, int kind, uint64_t index, int operand = 0) {
-  info->defect_section = section;
-  info->defect_kind = kind;
-  info->defect_index = index;
-  info->defect_operand = operand;
-  return MH_ERR_INVALID;
-}
-
-uint64_t ec_pow2(uint64_t v, uint64_t least) {  // the least power of two >= max(least, v); v <= 2^24 here
-  uint64_t p = least;
-  while (p < v) p <<= 1;
-  return p;
-}
-}  // namespace
+#include "ledger_plan.hpp"
 
 extern "C" int mh_ec_traces_plan(const mh_ec_group* groups, size_t n_groups, const mh_ec_point* points, size_t n_points, const mh_ec_add_op* adds,
                                  size_t n_add, const mh_msm_expr* exprs, size_t n_exprs, const mh_msm_term* terms, size_t n_terms, int log_groups,
@@ -41,54 +22,53 @@ extern "C" int mh_ec_traces_plan(const mh_ec_group* groups, size_t n_groups, con
   info->n_add = n_add;
   info->n_exprs = n_exprs;
   info->n_terms = n_terms;
-  if (!groups && n_groups) return ec_defect(info, 0, 1, 0);
-  if (!points && n_points) return ec_defect(info, 1, 1, 0);
-  if (!adds && n_add) return ec_defect(info, 2, 1, 0);
-  if (!exprs && n_exprs) return ec_defect(info, 3, 1, 0, 0);
-  if (!terms && n_terms) return ec_defect(info, 3, 1, 0, 1);
+  if (!groups && n_groups) return plan_defect_in(info, 0, 1, 0);
+  if (!points && n_points) return plan_defect_in(info, 1, 1, 0);
+  if (!adds && n_add) return plan_defect_in(info, 2, 1, 0);
+  if (!exprs && n_exprs) return plan_defect_in(info, 3, 1, 0, 0);
+  if (!terms && n_terms) return plan_defect_in(info, 3, 1, 0, 1);
   // heights: a count above the limit is not multiplied
-  if (n_groups > EC_MAX_ROWS) return ec_defect(info, 0, 2, n_groups);
-  if (n_points > EC_MAX_ROWS) return ec_defect(info, 1, 2, n_points);
-  if (n_add > EC_MAX_ROWS / 4) return ec_defect(info, 2, 2, n_add);
-  if (n_terms > EC_MAX_ROWS) return ec_defect(info, 3, 2, n_terms);
+  if (n_groups > PLAN_MAX_ROWS) return plan_defect_in(info, 0, 2, n_groups);
+  if (n_points > PLAN_MAX_ROWS) return plan_defect_in(info, 1, 2, n_points);
+  if (n_add > PLAN_MAX_ROWS / 4) return plan_defect_in(info, 2, 2, n_add);
+  if (n_terms > PLAN_MAX_ROWS) return plan_defect_in(info, 3, 2, n_terms);
   const int logs[4] = {log_groups, log_points, log_add, log_msm};
   for (int s = 0; s < 4; s++)
-    if (logs[s] > 24) return ec_defect(info, s, 2, (uint64_t)logs[s]);
-  info->groups_rows_needed = ec_pow2(n_groups, 2);
-  info->points_rows_needed = ec_pow2(n_points, 2);
-  info->add_rows_needed = ec_pow2(4 * (uint64_t)(n_add ? n_add : 1), 4);
-  info->msm_rows_needed = ec_pow2(n_terms, 2);
-  info->groups_rows = log_groups >= 0 ? (uint64_t)1 << log_groups : info->groups_rows_needed;
-  info->points_rows = log_points >= 0 ? (uint64_t)1 << log_points : info->points_rows_needed;
-  info->add_rows = log_add >= 0 ? (uint64_t)1 << log_add : info->add_rows_needed;
-  info->msm_rows = log_msm >= 0 ? (uint64_t)1 << log_msm : info->msm_rows_needed;
-  if (log_groups < -1 || info->groups_rows < info->groups_rows_needed) return ec_defect(info, 0, 3, info->groups_rows_needed);
-  if (log_points < -1 || info->points_rows < info->points_rows_needed) return ec_defect(info, 1, 3, info->points_rows_needed);
-  if (log_add < -1 || info->add_rows < info->add_rows_needed) return ec_defect(info, 2, 3, info->add_rows_needed);
-  if (log_msm < -1 || info->msm_rows < info->msm_rows_needed) return ec_defect(info, 3, 3, info->msm_rows_needed);
+    if (logs[s] > 24) return plan_defect_in(info, s, 2, (uint64_t)logs[s]);
+  info->groups_rows_needed = pow2_at_least(n_groups, 2);
+  info->points_rows_needed = pow2_at_least(n_points, 2);
+  info->add_rows_needed = pow2_at_least(4 * (uint64_t)n_add, 4);
+  info->msm_rows_needed = pow2_at_least(n_terms, 2);
+  // all four heights are written before the first that does not fit is refused
+  const uint64_t needed[4] = {info->groups_rows_needed, info->points_rows_needed, info->add_rows_needed, info->msm_rows_needed};
+  uint64_t* const rows[4] = {&info->groups_rows, &info->points_rows, &info->add_rows, &info->msm_rows};
+  bool fits[4];
+  for (int s = 0; s < 4; s++) fits[s] = plan_height(logs[s], needed[s], rows[s]);
+  for (int s = 0; s < 4; s++)
+    if (!fits[s]) return plan_defect_in(info, s, 3, needed[s]);
   for (size_t i = 0; i < n_points; i++)
-    if (points[i].group == 0 || points[i].group > n_groups) return ec_defect(info, 1, 4, i);
+    if (points[i].group == 0 || points[i].group > n_groups) return plan_defect_in(info, 1, 4, i);
   for (size_t i = 0; i < n_points; i++) {
     const mh_ec_point& p = points[i];
-    if (p.kind > 2) return ec_defect(info, 1, 5, i, 0);
-    if (p.kind == 1 && (p.x_ptr || p.y_ptr)) return ec_defect(info, 1, 5, i, p.x_ptr ? 1 : 2);
-    if (p.kind != 0 && (p.u_ptr || p.w_ptr)) return ec_defect(info, 1, 5, i, p.u_ptr ? 3 : 4);
+    if (p.kind > 2) return plan_defect_in(info, 1, 5, i, 0);
+    if (p.kind == 1 && (p.x_ptr || p.y_ptr)) return plan_defect_in(info, 1, 5, i, p.x_ptr ? 1 : 2);
+    if (p.kind != 0 && (p.u_ptr || p.w_ptr)) return plan_defect_in(info, 1, 5, i, p.u_ptr ? 3 : 4);
   }
   {
     uint64_t sum = 0;
     for (size_t k = 0; k < n_exprs; k++) {
       const mh_msm_expr& e = exprs[k];
-      if (e.kind > 2) return ec_defect(info, 3, 6, k, 0);
-      if (e.n_rows == 0 || (e.kind == 0 && e.n_rows != 1)) return ec_defect(info, 3, 6, k, 1);
+      if (e.kind > 2) return plan_defect_in(info, 3, 6, k, 0);
+      if (e.n_rows == 0 || (e.kind == 0 && e.n_rows != 1)) return plan_defect_in(info, 3, 6, k, 1);
       sum += e.n_rows;  // at most 2^64 / 2^32 records of less than 2^32 each: no wrap
     }
-    if (sum != n_terms) return ec_defect(info, 3, 6, n_exprs, 2);
+    if (sum != n_terms) return plan_defect_in(info, 3, 6, n_exprs, 2);
   }
   for (size_t k = 0; k < n_exprs; k++) {
     const mh_msm_expr& e = exprs[k];
     const bool a_bad = e.kind == 0 ? e.a_expr != 0 : (e.a_expr == 0 || e.a_expr > k);  // expression k is pointer k + 1: the earlier ones are 1..k
     const bool b_bad = e.kind == 1 ? (e.b_expr == 0 || e.b_expr > k) : e.b_expr != 0;
-    if (a_bad || b_bad) return ec_defect(info, 3, 7, k, a_bad ? 0 : 1);
+    if (a_bad || b_bad) return plan_defect_in(info, 3, 7, k, a_bad ? 0 : 1);
   }
   if (row_start) {
     uint32_t at = 0;

@@ -7,6 +7,7 @@
 #pragma once
 #include "../../include/midenhip.h"
 #include "gl.cuh"
+#include "ledger_stage.cuh"
 #include "wave_count.cuh"
 
 namespace {
@@ -26,19 +27,8 @@ struct EcLists {
   unsigned long long* defect;
 };
 
-#define EC_HD __host__ __device__ __forceinline__
-
-EC_HD void ec_report(unsigned long long* defect, int kind, int section, u32 index, int operand) {
-  const unsigned long long key = ((unsigned long long)kind << 56) | ((unsigned long long)section << 54) | ((unsigned long long)index << 8) | (unsigned long long)operand;
-#ifdef __HIP_DEVICE_COMPILE__
-  atomicMin(defect, key);
-#else
-  if (key < *defect) *defect = key;
-#endif
-}
-
 // the first of `n` terms whose base is not below `base` (n when there is none): the merge's cursor in front of `base`
-EC_HD u32 ec_lower_bound(const mh_msm_term* terms, u32 n, u32 base) {
+GL_HD u32 ec_lower_bound(const mh_msm_term* terms, u32 n, u32 base) {
   u32 lo = 0, hi = n;
   while (lo < hi) {
     const u32 mid = lo + (hi - lo) / 2;
@@ -48,7 +38,7 @@ EC_HD u32 ec_lower_bound(const mh_msm_term* terms, u32 n, u32 base) {
 }
 
 // the expression that holds term row t < n_terms: the last k with row_start[k] <= t
-EC_HD u32 ec_expr_of(const EcLists& L, u32 t) {
+GL_HD u32 ec_expr_of(const EcLists& L, u32 t) {
   u32 lo = 0, hi = L.n_exprs;
   while (hi - lo > 1) {
     const u32 mid = lo + (hi - lo) / 2;
@@ -57,36 +47,36 @@ EC_HD u32 ec_expr_of(const EcLists& L, u32 t) {
   return lo;
 }
 
-EC_HD u64 ec_mult(u64 ext, u32 count) { return gl_add(gl_canon(ext), (u64)count); }
+GL_HD u64 ec_mult(u64 ext, u32 count) { return gl_add(gl_canon(ext), (u64)count); }
 
 // ---- the counting and checking pass ----
 // every stored point reads its group (the planner has ranged `group`)
-EC_HD void ec_point_check(const EcLists& L, u32 i) { wave_count(&L.gcount[L.points[i].group - 1]); }
+GL_HD void ec_point_check(const EcLists& L, u32 i) { wave_count(&L.gcount[L.points[i].group - 1]); }
 
-EC_HD void ec_add_check(const EcLists& L, u32 i) {
+GL_HD void ec_add_check(const EcLists& L, u32 i) {
   const mh_ec_add_op op = L.adds[i];
   const bool bad_p = op.p == 0 || op.p > L.n_points, bad_q = op.q == 0 || op.q > L.n_points, bad_r = op.r == 0 || op.r > L.n_points,
              bad_g = op.group == 0 || op.group > L.n_groups;
   if (bad_p || bad_q || bad_r || bad_g) {
-    ec_report(L.defect, 8, 2, i, bad_p ? 0 : bad_q ? 1 : bad_r ? 2 : 3);
+    ledger_report(L.defect, 8, 2, i, bad_p ? 0 : bad_q ? 1 : bad_r ? 2 : 3);
     return;
   }
   if (op.kind > 5 || op.mints > 1 || (op.mints && op.kind < 4)) {
-    ec_report(L.defect, 9, 2, i, op.kind > 5 ? 0 : 1);
+    ledger_report(L.defect, 9, 2, i, op.kind > 5 ? 0 : 1);
     return;
   }
   const mh_ec_point p = L.points[op.p - 1], q = L.points[op.q - 1], r = L.points[op.r - 1];
   if (p.group != op.group || q.group != op.group || r.group != op.group) {
-    ec_report(L.defect, 10, 2, i, p.group != op.group ? 0 : q.group != op.group ? 1 : 2);
+    ledger_report(L.defect, 10, 2, i, p.group != op.group ? 0 : q.group != op.group ? 1 : 2);
     return;
   }
   const bool pai_p = p.kind == 1, pai_q = q.kind == 1;
   if (!(pai_p && pai_q ? op.kind == 2 : pai_p ? op.kind == 0 : pai_q ? op.kind == 1 : op.kind >= 3)) {
-    ec_report(L.defect, 11, 2, i, 0);
+    ledger_report(L.defect, 11, 2, i, 0);
     return;
   }
   if (op.mints && (op.r <= op.p || op.r <= op.q || r.kind != 2)) {
-    ec_report(L.defect, 12, 2, i, op.r <= op.p ? 0 : op.r <= op.q ? 1 : 2);
+    ledger_report(L.defect, 12, 2, i, op.r <= op.p ? 0 : op.r <= op.q ? 1 : 2);
     return;
   }
   wave_count(&L.pcount[op.p - 1]);
@@ -98,20 +88,20 @@ EC_HD void ec_add_check(const EcLists& L, u32 i) {
 }
 
 // the planner has ranged kind, n_rows and the operands: a_expr, b_expr name earlier expressions wherever the kind has them
-EC_HD void ec_expr_check(const EcLists& L, u32 k) {
+GL_HD void ec_expr_check(const EcLists& L, u32 k) {
   const mh_msm_expr e = L.exprs[k];
   const bool bad_v = e.val == 0 || e.val > L.n_points, bad_g = e.group == 0 || e.group > L.n_groups;
   if (bad_v || bad_g) {
-    ec_report(L.defect, 8, 3, k, bad_v ? 0 : 1);
+    ledger_report(L.defect, 8, 3, k, bad_v ? 0 : 1);
     return;
   }
   const u32 a_group = e.kind != 0 ? L.exprs[e.a_expr - 1].group : e.group, b_group = e.kind == 1 ? L.exprs[e.b_expr - 1].group : e.group;
   if (L.points[e.val - 1].group != e.group || a_group != e.group || b_group != e.group) {
-    ec_report(L.defect, 10, 3, k, L.points[e.val - 1].group != e.group ? 0 : a_group != e.group ? 1 : 2);
+    ledger_report(L.defect, 10, 3, k, L.points[e.val - 1].group != e.group ? 0 : a_group != e.group ? 1 : 2);
     return;
   }
   if (e.kind == 0) {
-    if (L.terms[L.row_start[k]].base != e.val) ec_report(L.defect, 15, 3, k, 0);
+    if (L.terms[L.row_start[k]].base != e.val) ledger_report(L.defect, 15, 3, k, 0);
     return;
   }
   wave_count(&L.gcount[e.group - 1]);
@@ -132,7 +122,7 @@ struct EcMerge {
   bool take_a, take_b;
 };
 
-EC_HD EcMerge ec_merge_at(const EcLists& L, const mh_msm_expr& e, u32 base) {
+GL_HD EcMerge ec_merge_at(const EcLists& L, const mh_msm_expr& e, u32 base) {
   EcMerge m;
   m.sa = L.row_start[e.a_expr - 1]; m.la = L.exprs[e.a_expr - 1].n_rows;
   m.sb = L.row_start[e.b_expr - 1]; m.lb = L.exprs[e.b_expr - 1].n_rows;
@@ -143,19 +133,19 @@ EC_HD EcMerge ec_merge_at(const EcLists& L, const mh_msm_expr& e, u32 base) {
   return m;
 }
 
-EC_HD void ec_term_check(const EcLists& L, u32 t) {
+GL_HD void ec_term_check(const EcLists& L, u32 t) {
   const u32 k = ec_expr_of(L, t);
   const mh_msm_expr e = L.exprs[k];
   const u32 idx = t - L.row_start[k], base = L.terms[t].base;
   if (idx > 0 && L.terms[t - 1].base >= base) {
-    ec_report(L.defect, 13, 3, t, 0);
+    ledger_report(L.defect, 13, 3, t, 0);
     return;
   }
   const bool last = idx + 1 == e.n_rows;
   if (e.kind == 1) {
     const EcMerge m = ec_merge_at(L, e, base);
     if (!m.take_a && !m.take_b) {
-      ec_report(L.defect, 14, 3, t, 0);
+      ledger_report(L.defect, 14, 3, t, 0);
       return;
     }
     u32 ni = m.la, nj = m.lb;  // where the walk stands after this row: the next row's cursors, or both lists' ends
@@ -164,15 +154,15 @@ EC_HD void ec_term_check(const EcLists& L, u32 t) {
       ni = ec_lower_bound(L.terms + m.sa, m.la, next);
       nj = ec_lower_bound(L.terms + m.sb, m.lb, next);
     }
-    if ((idx == 0 && (m.i != 0 || m.j != 0)) || m.i + (m.take_a ? 1u : 0u) != ni || m.j + (m.take_b ? 1u : 0u) != nj) ec_report(L.defect, 14, 3, t, 1);
+    if ((idx == 0 && (m.i != 0 || m.j != 0)) || m.i + (m.take_a ? 1u : 0u) != ni || m.j + (m.take_b ? 1u : 0u) != nj) ledger_report(L.defect, 14, 3, t, 1);
   } else if (e.kind == 2) {
     const u32 sa = L.row_start[e.a_expr - 1], la = L.exprs[e.a_expr - 1].n_rows;
-    if (idx >= la || L.terms[sa + idx].base != base || (last && e.n_rows != la)) ec_report(L.defect, 14, 3, t, 2);
+    if (idx >= la || L.terms[sa + idx].base != base || (last && e.n_rows != la)) ledger_report(L.defect, 14, 3, t, 2);
   }
 }
 
 // ---- rows: the pass above has been read back clean, every pointer below is in range ----
-EC_HD void ec_groups_row(const EcLists& L, u64 n, u64* __restrict__ out, u64 t) {
+GL_HD void ec_groups_row(const EcLists& L, u64 n, u64* __restrict__ out, u64 t) {
   u64 s[EC_GROUPS_WIDTH];
 #pragma unroll
   for (int c = 0; c < EC_GROUPS_WIDTH; c++) s[c] = 0;
@@ -186,7 +176,7 @@ EC_HD void ec_groups_row(const EcLists& L, u64 n, u64* __restrict__ out, u64 t) 
   for (int c = 0; c < EC_GROUPS_WIDTH; c++) out[(size_t)c * n + t] = s[c];
 }
 
-EC_HD void ec_points_row(const EcLists& L, u64 n, u64* __restrict__ out, u64 t) {
+GL_HD void ec_points_row(const EcLists& L, u64 n, u64* __restrict__ out, u64 t) {
   u64 s[EC_POINTS_WIDTH];
 #pragma unroll
   for (int c = 0; c < EC_POINTS_WIDTH; c++) s[c] = 0;
@@ -206,7 +196,7 @@ EC_HD void ec_points_row(const EcLists& L, u64 n, u64* __restrict__ out, u64 t) 
 }
 
 // addition t / 4, role t % 4: slope, tail, result, term
-EC_HD void ec_add_row(const EcLists& L, u64 n, u64* __restrict__ out, u64 t) {
+GL_HD void ec_add_row(const EcLists& L, u64 n, u64* __restrict__ out, u64 t) {
   const u64 i = t >> 2;
   const int role = (int)(t & 3);
   u64 s[EC_ADD_WIDTH];
@@ -243,7 +233,7 @@ EC_HD void ec_add_row(const EcLists& L, u64 n, u64* __restrict__ out, u64 t) {
   for (int c = 0; c < EC_ADD_WIDTH; c++) out[(size_t)c * n + t] = s[c];
 }
 
-EC_HD void ec_msm_row(const EcLists& L, u64 n, u64* __restrict__ out, u64 t) {
+GL_HD void ec_msm_row(const EcLists& L, u64 n, u64* __restrict__ out, u64 t) {
   u64 s[EC_MSM_WIDTH];
 #pragma unroll
   for (int c = 0; c < EC_MSM_WIDTH; c++) s[c] = 0;

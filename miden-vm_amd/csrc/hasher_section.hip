@@ -635,9 +635,7 @@ struct HsBuildTarget : HsTarget {
     if (l < 0)
       for (l = 6; ((u64)1 << l) < n_rows; l++) {}  // n_rows <= 2^25
     const u64 height = (u64)1 << l;
-    t.reset(new mh_trace());
-    t->ctx = c; t->log_n = l; t->width = HS_WIDTH;
-    t->cols.alloc(height * HS_WIDTH * 8);
+    t = trace_new(c, l, HS_WIDTH);
     if (n_rows < height)  // rows [n_rows, height) of every column
       HIP_CHECK(hipMemset2DAsync(t->cols.u() + n_rows, height * 8, 0, (height - n_rows) * 8, HS_WIDTH, c->stream));
     *out_log_n = l;

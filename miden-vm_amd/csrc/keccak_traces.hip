@@ -433,13 +433,6 @@ inline u64 kt_round_height(u64 n_perms) {  // max(2, next_pow2(ceil(max(n, 1) / 
 inline u64 kt_sponge_height(u64 n_blocks) { return n_blocks ? kt_pow2_at_least(KT_SPONGE_PERIOD * n_blocks) : KT_SPONGE_PERIOD; }
 constexpr u64 KT_MAX_PERMS = 2 * (SEC_MAX_ROWS / KT_CYCLE);  // the round trace of more permutations is above 2^24 rows
 
-std::unique_ptr<mh_trace> kt_new_trace(mh_ctx* c, int log_n, size_t width) {
-  std::unique_ptr<mh_trace> t(new mh_trace());
-  t->ctx = c; t->log_n = log_n; t->width = width;
-  t->cols.alloc(((size_t)1 << log_n) * width * 8);
-  return t;
-}
-
 void kt_round_rows(mh_ctx* c, const u64* image, const KtTab* tab, u64 n_perms, mh_trace* t) {
   const u64 height = (u64)1 << t->log_n;
   ProfScope ps(c, "kt_round_rows", (16.0 + 8.0 * KT_BAND) * 2.0 * (double)height);
@@ -496,7 +489,7 @@ extern "C" int mh_keccak_round_trace_build(mh_ctx* c, const uint64_t* states, si
     kt_table(tab);
     DevBuf dtab(sizeof tab), dstates(n_perms * 200), image(n_perms * KT_WORDS * 8), dout(outputs ? n_perms * 200 : 0);
     c->h2d(dtab.p, &tab, sizeof tab);
-    std::unique_ptr<mh_trace> t = kt_new_trace(c, log_n, KT_ROUND_WIDTH);
+    std::unique_ptr<mh_trace> t = trace_new(c, log_n, KT_ROUND_WIDTH);
     if (n_perms) {
       c->h2d(dstates.p, states, n_perms * 200);
       KtRun r{(const KtTab*)dtab.p, nullptr, nullptr, nullptr, dstates.u(), image.u(), nullptr, nullptr, dout.u(), nullptr};
@@ -547,7 +540,7 @@ extern "C" int mh_keccak_traces_build(mh_ctx* c, const uint8_t* bytes, size_t n_
     DevBuf dtab(sizeof tab), dbytes(n_bytes), dmsgs(n_msgs * sizeof(mh_keccak_msg)), block_off((n_msgs + 1) * 4), agg((size_t)tiles * 8), totals(16);
     DevBuf image(n_blocks * KT_WORDS * 8), at_start(n_blocks * 200), post16(n_blocks * 8), perm_out(n_blocks * 200), ddig(digests ? n_msgs * 32 : 0);
     c->h2d(dtab.p, &tab, sizeof tab);
-    std::unique_ptr<mh_trace> rt = kt_new_trace(c, log_round, KT_ROUND_WIDTH), st = kt_new_trace(c, log_sponge, KT_SPONGE_WIDTH);
+    std::unique_ptr<mh_trace> rt = trace_new(c, log_round, KT_ROUND_WIDTH), st = trace_new(c, log_sponge, KT_SPONGE_WIDTH);
     long long pad_bytes_left = 0;
     u64 pad_chunk_ptr = 0;
     if (n_msgs) {

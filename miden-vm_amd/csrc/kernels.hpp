@@ -41,6 +41,18 @@ struct mh_trace {
     if (ready) (void)hipEventDestroy(ready);
   }
 };
+// The one way to make a trace: 2^log_n rows of `width` columns, allocated (width 0: nothing) and not zeroed.
+inline std::unique_ptr<mh_trace> trace_new(mh_ctx* c, int log_n, size_t width) {
+  std::unique_ptr<mh_trace> t(new mh_trace());
+  t->ctx = c; t->log_n = log_n; t->width = width;
+  t->cols.alloc(((size_t)1 << log_n) * width * 8);
+  return t;
+}
+inline int ceil_log2(u64 rows) {  // for a builder that holds a row count: the least l with 2^l >= rows
+  int l = 0;
+  while (((u64)1 << l) < rows) l++;
+  return l;
+}
 // Order everything enqueued on c->stream from here on after the trace's upload (no-op for a synchronously uploaded trace).
 void trace_wait_ready(mh_ctx* c, const mh_trace* t);
 mh_trace* trace_upload_cols_async(mh_ctx* c, const u64* colmajor, int log_n, size_t width);

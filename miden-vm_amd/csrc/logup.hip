@@ -307,9 +307,7 @@ mh_trace* lookup_build_aux(mh_ctx* c, const mh_lookup* lk, const mh_trace* main,
   c->h2d(dcount.p, lk->col_count.data(), lk->col_count.size() * 4);
   c->h2d(dext.p, lk->out_ext.data(), lk->out_ext.size());
   HIP_CHECK(hipMemsetAsync(derr.p, 0, 4, c->stream));
-  std::unique_ptr<mh_trace> aux(new mh_trace());
-  aux->ctx = c; aux->log_n = log_n; aux->width = 2 * lk->num_aux_cols();
-  aux->cols.alloc(aux->width * n * 8);
+  std::unique_ptr<mh_trace> aux = trace_new(c, log_n, 2 * lk->num_aux_cols());
   DevBuf totals(2 * n * 8);
   const size_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
   DevBuf tile_sums(2 * tiles * 8), grand(2 * 8);

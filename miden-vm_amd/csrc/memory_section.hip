@@ -578,9 +578,7 @@ extern "C" int mh_memory_section_build(mh_ctx* c, const mh_mem_access* accesses,
     const u64 height = (u64)1 << log_n;
     if (n > height) ms_refuse(info, 0, 0, log_n, 4, height, accesses, entry);
     HIP_CHECK(hipSetDevice(c->device));
-    std::unique_ptr<mh_trace> t(new mh_trace());
-    t->ctx = c; t->log_n = log_n; t->width = MS_WIDTH;
-    t->cols.alloc(height * MS_WIDTH * 8);
+    std::unique_ptr<mh_trace> t = trace_new(c, log_n, MS_WIDTH);
     if (n < height)  // rows [n, height) of every column
       HIP_CHECK(hipMemset2DAsync(t->cols.u() + n, height * 8, 0, (height - n) * 8, MS_WIDTH, c->stream));
     ms_fill_info(info, 0, 0, 0, log_n, 0, 0);

@@ -259,9 +259,7 @@ mh_trace* p2t_build(mh_ctx* c, P2tCycles a, u64 n_input, int log_n, mh_p2_trace_
     p2t_refuse(info, a.k, n_input, shown, 4, (((u64)1 << shown) >> 4) - 1, entry);
   }
   const u64 n = (u64)1 << log_n;
-  std::unique_ptr<mh_trace> t(new mh_trace());
-  t->ctx = c; t->log_n = log_n; t->width = P2T_WIDTH;
-  t->cols.alloc(n * P2T_WIDTH * 8);
+  std::unique_ptr<mh_trace> t = trace_new(c, log_n, P2T_WIDTH);
   a.n = n;
   a.cycles = n / P2T_CYCLE;
   a.out = t->cols.u();

@@ -326,9 +326,7 @@ extern "C" int mh_poseidon2_chiplet_trace_build(mh_ctx* c, const mh_p2c_absorpti
     HIP_CHECK(hipSetDevice(c->device));
     DevBuf dabs(n_abs * sizeof(mh_p2c_absorption)), dstart(n_abs * 8), dorder(n_abs * 4), dlevel_off((size_t)(n_levels + 1) * 4), dblocks(n_cycles * 64),
         drefs(refs ? n_cycles * 16 : 0), rec(n_cycles * P2C_REC * 8), ddig(n_abs * 32), dout(outputs ? n_cycles * 96 : 0);
-    std::unique_ptr<mh_trace> t(new mh_trace());
-    t->ctx = c; t->log_n = log_n; t->width = P2C_WIDTH;
-    t->cols.alloc(height * P2C_WIDTH * 8);
+    std::unique_ptr<mh_trace> t = trace_new(c, log_n, P2C_WIDTH);
     if (n_abs) {
       c->h2d(dabs.p, abs, n_abs * sizeof(mh_p2c_absorption));
       c->h2d(dstart.p, start.data(), n_abs * 8);

@@ -40,11 +40,9 @@ std::vector<u64> coset_shifts(int log_n, int lb) {
 
 mh_trace* trace_upload(mh_ctx* c, const u64* rowmajor, int log_n, size_t width) {
   size_t n = (size_t)1 << log_n;
-  std::unique_ptr<mh_trace> t(new mh_trace());
-  t->ctx = c; t->log_n = log_n; t->width = width;
+  std::unique_ptr<mh_trace> t = trace_new(c, log_n, width);
   if (width == 0) return t.release();
   DevBuf staging(n * width * 8);
-  t->cols.alloc(n * width * 8);
   HIP_CHECK(hipMemcpyAsync(staging.p, rowmajor, n * width * 8, hipMemcpyHostToDevice, c->stream));
   {
     ProfScope ps(c, "transpose_in", 16.0 * n * width);
@@ -62,12 +60,10 @@ mh_trace* trace_upload(mh_ctx* c, const u64* rowmajor, int log_n, size_t width) 
 // read-tag limit for 64-216 B segments, tools/h2dbench, and every column NTT needs all rows.)
 mh_trace* trace_upload_async(mh_ctx* c, const u64* rowmajor, int log_n, size_t width) {
   size_t n = (size_t)1 << log_n;
-  std::unique_ptr<mh_trace> t(new mh_trace());
-  t->ctx = c; t->log_n = log_n; t->width = width;
+  std::unique_ptr<mh_trace> t = trace_new(c, log_n, width);
   if (width == 0) return t.release();
   if (!c->copy_stream) HIP_CHECK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
   t->staging.alloc(n * width * 8);
-  t->cols.alloc(n * width * 8);
   // pooled buffers: whatever the compute stream still does with their previous contents comes first
   hipEvent_t fence = c->get_event();
   HIP_CHECK(hipEventRecord(fence, c->stream));
@@ -88,11 +84,9 @@ __global__ void k_canon_inplace(u64* p, size_t n) {
 }
 mh_trace* trace_upload_cols_async(mh_ctx* c, const u64* colmajor, int log_n, size_t width) {
   const size_t n = (size_t)1 << log_n;
-  std::unique_ptr<mh_trace> t(new mh_trace());
-  t->ctx = c; t->log_n = log_n; t->width = width;
+  std::unique_ptr<mh_trace> t = trace_new(c, log_n, width);
   if (width == 0) return t.release();
   if (!c->copy_stream) HIP_CHECK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  t->cols.alloc(n * width * 8);
   hipEvent_t fence = c->get_event();  // pooled buffer: whatever the compute stream still does with its previous contents comes first
   HIP_CHECK(hipEventRecord(fence, c->stream));
   HIP_CHECK(hipStreamWaitEvent(c->copy_stream, fence, 0));
@@ -126,9 +120,7 @@ void trace_wait_ready(mh_ctx* c, const mh_trace* t) {
 
 mh_trace* trace_zeros(mh_ctx* c, int log_n, size_t width) {
   size_t n = (size_t)1 << log_n;
-  std::unique_ptr<mh_trace> t(new mh_trace());
-  t->ctx = c; t->log_n = log_n; t->width = width;
-  t->cols.alloc(n * width * 8);
+  std::unique_ptr<mh_trace> t = trace_new(c, log_n, width);
   if (width) HIP_CHECK(hipMemsetAsync(t->cols.p, 0, n * width * 8, c->stream));
   return t.release();
 }
@@ -1135,10 +1127,8 @@ int mh_trace_upload_sharded(mh_ctx* c, const mh_comm* comm, const uint64_t* rowm
     d.comm = comm; d.rank = comm->rank; d.world = comm->world;
     while ((1 << d.logG) < d.world) d.logG++;
     const size_t rows = n / comm->world, slice = rows * width * 8;
-    std::unique_ptr<mh_trace> t(new mh_trace());
-    t->ctx = c; t->log_n = log_n; t->width = width;
+    std::unique_ptr<mh_trace> t = trace_new(c, log_n, width);
     DevBuf mine(slice), full(n * width * 8);
-    t->cols.alloc(n * width * 8);
     HIP_CHECK(hipMemcpyAsync(mine.p, rowmajor + (size_t)comm->rank * rows * width, slice, hipMemcpyHostToDevice, c->stream));
     d.all_gather(c, mine.p, full.p, slice);  // rank order = row order
     {

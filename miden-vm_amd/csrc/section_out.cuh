@@ -45,9 +45,7 @@ inline int sec_log_n(u64 rows) {  // max(6, ceil log2 rows)
 // a fresh trace of `width` columns whose rows [n_rows, 2^log_n) are zero; rows [0, n_rows) are the caller's to write
 inline std::unique_ptr<mh_trace> sec_new_trace(mh_ctx* c, int log_n, size_t width, u64 n_rows) {
   const u64 height = (u64)1 << log_n;
-  std::unique_ptr<mh_trace> t(new mh_trace());
-  t->ctx = c; t->log_n = log_n; t->width = width;
-  t->cols.alloc(height * width * 8);
+  std::unique_ptr<mh_trace> t = trace_new(c, log_n, width);
   if (n_rows < height) HIP_CHECK(hipMemset2DAsync(t->cols.u() + n_rows, height * 8, 0, (height - n_rows) * 8, width, c->stream));
   return t;
 }

@@ -9,16 +9,17 @@
 // message bytes, the Keccak digests and 64 bytes a record; the transcript as 64 bytes a node, 8 a term row and 32 a literal.  The
 // planners (transcript_traces_plan.cpp, host only) have ranged every index and cycle and given the heights and every node's first row.
 // Each build has two stages with one read-back between them:
-//   check    k_cn_chunk_check   a lane per chunk row: is_absorb of its cycle is 0 on a chain's head and 1 behind it.
-//            k_cn_record_check  a lane per record: the three digest cycles end an absorption.
-//            k_te_row_check     a lane per active row: its node by a search over the first rows; the operands' classes, moduli and
+//   check    cn_chunk_check     a lane per chunk row: is_absorb of its cycle is 0 on a chain's head and 1 behind it.
+//            cn_record_check    a lane per record: the three digest cycles end an absorption.
+//            te_row_check       a lane per active row: its node by a search over the first rows; the operands' classes, moduli and
 //                               `is` pointers, the node's cycle (an MSM row's: its place in the span) against the absorptions, and the
 //                               reads of the operands, integers added once per wave where the lanes agree (wave_count.cuh).
-//            k_te_read_check    a lane per node, behind the counting: a truthy node is read once, the root never, a value node at all.
+//            te_read_check      a lane per node, behind the counting: a truthy node is read once, the root never, a value node at all.
 //            Defects (kinds 8..) go into one packed 64-bit minimum: kind, index, operand.
-//   rows     after the minimum has been read back clean and the trace is allocated: k_cn_rows, k_te_rows, a lane per trace row, padding
+//   rows     after the minimum has been read back clean and the trace is allocated: cn_row, te_row, a lane per trace row, padding
 //            included.  Consecutive lanes hold consecutive rows of a column-major column: every store is a whole line.
-// The bodies are in transcript_traces_rows.cuh.  The counters and the minimum are scratch that the call clears itself; every cell has
+// The bodies named above are in transcript_traces_rows.cuh; their kernels are ledger_stage.cuh's lane_per_record<body> and
+// lane_per_row<body>, as the defect word, its read-back and the refusal's message are.  The counters and the minimum are scratch that the call clears itself; every cell has
 // exactly one writer: a second call leaves the same bytes.  No LDS.
 #include "section_out.cuh"
 #include "transcript_traces_rows.cuh"
@@ -32,39 +33,6 @@ static_assert(sizeof(mh_transcript_eval_info) == 80, "mh_transcript_eval_info is
 
 namespace {
 constexpr int TT_BT = 256;
-}
-
-__global__ __launch_bounds__(TT_BT) void k_cn_chunk_check(CnLists L) {
-  const u32 t = blockIdx.x * TT_BT + threadIdx.x;
-  if (t < L.total_chunks) cn_chunk_check(L, t);
-}
-
-__global__ __launch_bounds__(TT_BT) void k_cn_record_check(CnLists L) {
-  const u32 i = blockIdx.x * TT_BT + threadIdx.x;
-  if (i < L.n) cn_record_check(L, i);
-}
-
-__global__ __launch_bounds__(TT_BT) void k_cn_rows(CnLists L, u64 n, u64* __restrict__ out) {
-  const u64 t = (u64)blockIdx.x * TT_BT + threadIdx.x;
-  if (t < n) cn_row(L, n, out, t);
-}
-
-__global__ __launch_bounds__(TT_BT) void k_te_row_check(TeLists L) {
-  const u32 r = blockIdx.x * TT_BT + threadIdx.x;
-  if (r < L.n_body) te_row_check(L, r);
-}
-
-__global__ __launch_bounds__(TT_BT) void k_te_read_check(TeLists L) {
-  const u32 i = blockIdx.x * TT_BT + threadIdx.x;
-  if (i < L.n_nodes) te_read_check(L, i);
-}
-
-__global__ __launch_bounds__(TT_BT) void k_te_rows(TeLists L, u64 n, u64* __restrict__ out) {
-  const u64 r = (u64)blockIdx.x * TT_BT + threadIdx.x;
-  if (r < n) te_row(L, n, out, r);
-}
-
-namespace {
 const char* const CN_WHAT[] = {"",
                                "a null pointer where one is required, or a p2 that is not a 32-column trace of this context",
                                "offset + len past n_bytes",
@@ -94,10 +62,7 @@ const char* const TE_WHAT[] = {"",
 
 template <class Info>
 [[noreturn]] void tt_refuse(const char* entry, const Info* info, const char* const* what) {
-  char buf[320];
-  snprintf(buf, sizeof buf, "%s: defect %d, index %llu, operand %d: %s", entry, info->defect_kind, (unsigned long long)info->defect_index,
-           info->defect_operand, what[info->defect_kind]);
-  throw MhError(MH_ERR_INVALID, buf);
+  ledger_refuse(entry, {info->defect_kind, -1, info->defect_index, info->defect_operand}, what[info->defect_kind]);
 }
 
 // kind 1, operands 3 and 4: the Poseidon2 trace and the out pointer
@@ -113,23 +78,10 @@ void tt_require_args(mh_ctx* c, const mh_trace* p2, const void* out, const char*
 
 template <class Info>
 void tt_read_defect(mh_ctx* c, const DevBuf& ddefect, int last_kind, const char* entry, Info* info, const char* const* what) {
-  unsigned long long defect = 0;
-  c->d2h(&defect, ddefect.p, 8);  // waits for the checking pass: nothing is allocated for the trace before it is known clean
-  if (defect == ~0ull) return;
-  info->defect_kind = (int32_t)(defect >> 56);
-  info->defect_index = (defect >> 8) & 0xffffffffull;
-  info->defect_operand = (int32_t)(defect & 0xff);
-  MH_REQUIRE(info->defect_kind >= 8 && info->defect_kind <= last_kind, std::string(entry) + ": the checking pass left an unreadable defect word");
+  const LedgerDefect d = ledger_read_defect(c, ddefect.p, 8, last_kind, entry, "checking");
+  if (!d.kind) return;
+  info->defect_kind = d.kind; info->defect_index = d.index; info->defect_operand = d.operand;
   tt_refuse(entry, info, what);
-}
-
-std::unique_ptr<mh_trace> tt_new_trace(mh_ctx* c, u64 rows, int width) {
-  int l = 0;
-  while (((u64)1 << l) < rows) l++;
-  std::unique_ptr<mh_trace> t(new mh_trace());
-  t->ctx = c; t->log_n = l; t->width = width;
-  t->cols.alloc(rows * width * 8);
-  return t;
 }
 
 P2View tt_p2(const mh_trace* p2) { return P2View{p2->cols.u(), (u64)1 << p2->log_n, ((u64)1 << p2->log_n) / P2_PERIOD}; }
@@ -161,18 +113,18 @@ extern "C" int mh_chunk_node_trace_build(mh_ctx* c, const mh_trace* p2, const ui
     if (n) {
       {
         ProfScope ps(c, "cn_chunk_check", (double)info->n_chunks * 8);
-        MH_LAUNCH(k_cn_chunk_check, dim3(sec_grid(info->n_chunks, TT_BT)), dim3(TT_BT), 0, c->stream, L);
+        launch_per_record<CnLists, &CnLists::total_chunks, cn_chunk_check, TT_BT>(c, L);
       }
       {
         ProfScope ps(c, "cn_record_check", (double)n * (sizeof(mh_kn_record) + 15 * 8));
-        MH_LAUNCH(k_cn_record_check, dim3(sec_grid(n, TT_BT)), dim3(TT_BT), 0, c->stream, L);
+        launch_per_record<CnLists, &CnLists::n, cn_record_check, TT_BT>(c, L);
       }
     }
     tt_read_defect(c, ddefect, 9, entry, info, CN_WHAT);
-    std::unique_ptr<mh_trace> t = tt_new_trace(c, info->rows, CN_WIDTH);
+    std::unique_ptr<mh_trace> t = trace_new(c, ceil_log2(info->rows), CN_WIDTH);
     {
       ProfScope ps(c, "cn_rows", 8.0 * CN_WIDTH * (double)info->rows);
-      MH_LAUNCH(k_cn_rows, dim3(sec_grid(info->rows, TT_BT)), dim3(TT_BT), 0, c->stream, L, (u64)info->rows, t->cols.u());
+      launch_per_row<CnLists, cn_row, TT_BT>(c, L, info->rows, t->cols.u());
     }
     // the lists are pooled buffers: they go back to the pool when this scope ends, ordered behind the row kernel on the stream
     *out = t.release();
@@ -213,17 +165,17 @@ extern "C" int mh_transcript_eval_trace_build(mh_ctx* c, const mh_trace* p2, con
                     (u32)root, n_body, info->n_zero, (u32*)dcount.p, view, (unsigned long long*)ddefect.p};
     {
       ProfScope ps(c, "te_row_check", (double)n_body * 3 * sizeof(mh_te_node));
-      MH_LAUNCH(k_te_row_check, dim3(sec_grid(n_body, TT_BT)), dim3(TT_BT), 0, c->stream, L);
+      launch_per_record<TeLists, &TeLists::n_body, te_row_check, TT_BT>(c, L);
     }
     {
       ProfScope ps(c, "te_read_check", (double)n_nodes * (sizeof(mh_te_node) + 4));
-      MH_LAUNCH(k_te_read_check, dim3(sec_grid(n_nodes, TT_BT)), dim3(TT_BT), 0, c->stream, L);
+      launch_per_record<TeLists, &TeLists::n_nodes, te_read_check, TT_BT>(c, L);
     }
     tt_read_defect(c, ddefect, 15, entry, info, TE_WHAT);
-    std::unique_ptr<mh_trace> t = tt_new_trace(c, info->rows, TE_WIDTH);
+    std::unique_ptr<mh_trace> t = trace_new(c, ceil_log2(info->rows), TE_WIDTH);
     {
       ProfScope ps(c, "te_rows", 8.0 * TE_WIDTH * (double)info->rows);
-      MH_LAUNCH(k_te_rows, dim3(sec_grid(info->rows, TT_BT)), dim3(TT_BT), 0, c->stream, L, (u64)info->rows, t->cols.u());
+      launch_per_row<TeLists, te_row, TT_BT>(c, L, info->rows, t->cols.u());
     }
     if (root_felts) {  // the statement's public input: row 0's h, four columns a height apart, in one copy
       HIP_CHECK(hipMemcpy2DAsync(root_felts, 8, t->cols.u() + (size_t)TEC_H * info->rows, info->rows * 8, 8, 4, hipMemcpyDeviceToHost, c->stream));

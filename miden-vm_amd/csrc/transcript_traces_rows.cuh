@@ -9,13 +9,12 @@
 #pragma once
 #include "../../include/midenhip.h"
 #include "gl.cuh"
+#include "ledger_stage.cuh"
 #include "wave_count.cuh"
 
 namespace {
 constexpr int CN_WIDTH = 42, CN_CHUNK_WIDTH = 12, TE_WIDTH = 39, P2_WIDTH = 32, P2_PERIOD = 16;
 constexpr int P2_COL_IS_ABSORB = 3, P2_COL_STATE = 4;
-
-#define TT_HD __host__ __device__ __forceinline__
 
 // the device-resident Poseidon2 chiplet trace, column-major: what mh_poseidon2_chiplet_trace_build returned
 struct P2View {
@@ -24,23 +23,18 @@ struct P2View {
   u64 cycles;  // n / 16
 };
 
-TT_HD u64 p2_is_absorb(const P2View& p, u64 c) { return p.cols[(size_t)P2_COL_IS_ABSORB * p.n + P2_PERIOD * c]; }
+GL_HD u64 p2_is_absorb(const P2View& p, u64 c) { return p.cols[(size_t)P2_COL_IS_ABSORB * p.n + P2_PERIOD * c]; }
 // lane j of the digest on cycle c: the permutation's output, row 15 of the cycle
-TT_HD u64 p2_digest(const P2View& p, u64 c, int j) { return p.cols[(size_t)(P2_COL_STATE + j) * p.n + P2_PERIOD * c + (P2_PERIOD - 1)]; }
+GL_HD u64 p2_digest(const P2View& p, u64 c, int j) { return p.cols[(size_t)(P2_COL_STATE + j) * p.n + P2_PERIOD * c + (P2_PERIOD - 1)]; }
 // cycle c < cycles is the last of an absorption: the next cycle starts one (or there is none), and c is not padding (all zero)
-TT_HD bool p2_ends(const P2View& p, u64 c) {
+GL_HD bool p2_ends(const P2View& p, u64 c) {
   if (c + 1 < p.cycles && p2_is_absorb(p, c + 1) != 0) return false;
   return (p2_digest(p, c, 0) | p2_digest(p, c, 1) | p2_digest(p, c, 2) | p2_digest(p, c, 3)) != 0;
 }
 
-TT_HD void tt_report(unsigned long long* defect, int kind, u64 index, int operand) {
-  const unsigned long long key = ((unsigned long long)kind << 56) | ((unsigned long long)(index & 0xffffffffull) << 8) | (unsigned long long)operand;
-#ifdef __HIP_DEVICE_COMPILE__
-  atomicMin(defect, key);
-#else
-  if (key < *defect) *defect = key;
-#endif
-}
+// These two builders have no sections: section 0, and an index held in 64 bits cut to its low 32.  (The bodies call this and not
+// ledger_report itself: with the cut at each call te_row_check's instruction stream changed, through here it is the one it was.)
+GL_HD void tt_report(unsigned long long* defect, int kind, u64 index, int operand) { ledger_report(defect, kind, 0, (u32)index, operand); }
 
 // ================================================ ChunkNode ================================================
 struct CnLists {
@@ -54,10 +48,10 @@ struct CnLists {
   unsigned long long* defect;
 };
 
-TT_HD u64 cn_n_chunks(u64 len) { return len ? (len + 31) / 32 : 1; }
+GL_HD u64 cn_n_chunks(u64 len) { return len ? (len + 31) / 32 : 1; }
 
 // the record whose chain holds chunk row t < total_chunks: the last i with chunk_head[i] <= t (the heads are the running sum)
-TT_HD u32 cn_record_of(const CnLists& L, u32 t) {
+GL_HD u32 cn_record_of(const CnLists& L, u32 t) {
   u32 lo = 0, hi = L.n;
   while (hi - lo > 1) {
     const u32 mid = lo + (hi - lo) / 2;
@@ -67,7 +61,7 @@ TT_HD u32 cn_record_of(const CnLists& L, u32 t) {
 }
 
 // a lane per chunk row: its cycle continues the chain's absorption, or starts it
-TT_HD void cn_chunk_check(const CnLists& L, u32 t) {
+GL_HD void cn_chunk_check(const CnLists& L, u32 t) {
   const u32 i = cn_record_of(L, t);
   const u64 c = t - L.records[i].chunk_head;
   const u64 a = p2_is_absorb(L.p2, L.records[i].perm_chunks + c);
@@ -75,7 +69,7 @@ TT_HD void cn_chunk_check(const CnLists& L, u32 t) {
 }
 
 // a lane per record: the three digests it reads end an absorption
-TT_HD void cn_record_check(const CnLists& L, u32 i) {
+GL_HD void cn_record_check(const CnLists& L, u32 i) {
   const mh_kn_record r = L.records[i];
   const u64 cyc[3] = {r.perm_chunks + cn_n_chunks(r.len) - 1, r.perm_digest_chunks, r.perm_keccak};
 #pragma unroll
@@ -86,7 +80,7 @@ TT_HD void cn_record_check(const CnLists& L, u32 i) {
     }
 }
 
-TT_HD u64 tt_le32(const uint8_t* b, u64 at, u64 end) {  // the little-endian u32 at `at`, bytes at and past `end` read as 0
+GL_HD u64 tt_le32(const uint8_t* b, u64 at, u64 end) {  // the little-endian u32 at `at`, bytes at and past `end` read as 0
   u64 v = 0;
   for (int k = 0; k < 4; k++)
     if (at + k < end) v |= (u64)b[at + k] << (8 * k);
@@ -94,7 +88,7 @@ TT_HD u64 tt_le32(const uint8_t* b, u64 at, u64 end) {  // the little-endian u32
 }
 
 // row t of the 42-column trace: the chunk side, then the node side
-TT_HD void cn_row(const CnLists& L, u64 n, u64* out, u64 t) {
+GL_HD void cn_row(const CnLists& L, u64 n, u64* out, u64 t) {
   u64 row[CN_WIDTH];
   for (int k = 0; k < CN_WIDTH; k++) row[k] = 0;
   row[0] = t;
@@ -158,7 +152,7 @@ struct TeLists {
   unsigned long long* defect;
 };
 
-TT_HD int te_class(const mh_te_node& x) {
+GL_HD int te_class(const mh_te_node& x) {
   switch (x.kind) {
     case TE_UINT_LEAF: return TE_CLASS_UINT;
     case TE_UINT_OP: return x.op == 4 ? TE_CLASS_TRUTHY : TE_CLASS_UINT;
@@ -169,9 +163,9 @@ TT_HD int te_class(const mh_te_node& x) {
 }
 
 // the cycle whose digest is the node's hash (an MSM's: its last); ZERO has none
-TT_HD u64 te_hash_cycle(const mh_te_node& x) { return x.kind == TE_EC_MSM ? x.perm + (u64)x.rhs - 1 : x.perm; }
+GL_HD u64 te_hash_cycle(const mh_te_node& x) { return x.kind == TE_EC_MSM ? x.perm + (u64)x.rhs - 1 : x.perm; }
 
-TT_HD u64 te_src_hash(const TeLists& L, int64_t src, int j) {
+GL_HD u64 te_src_hash(const TeLists& L, int64_t src, int j) {
   if (src < 0) return p2_digest(L.p2, (u64)(-1 - src), j);
   const mh_te_node x = L.nodes[src];
   return x.kind == TE_ZERO ? 0 : p2_digest(L.p2, te_hash_cycle(x), j);
@@ -179,7 +173,7 @@ TT_HD u64 te_src_hash(const TeLists& L, int64_t src, int j) {
 
 // the node of trace row 1 <= r < n_body (row 0 is the root's) and the row's place in it: the last i with row_start[i] <= r.  The root
 // and the ZEROs take no row here: they share their start with the node behind them, which the search prefers.
-TT_HD u32 te_node_of(const TeLists& L, u32 r, u32* idx) {
+GL_HD u32 te_node_of(const TeLists& L, u32 r, u32* idx) {
   if (r == 0) {
     *idx = 0;
     return L.root;
@@ -194,7 +188,7 @@ TT_HD u32 te_node_of(const TeLists& L, u32 r, u32* idx) {
 }
 
 // one binary operand of node i: its class, and its read.  -> false after a report
-TT_HD bool te_operand(const TeLists& L, u32 i, int64_t src, int want, int operand) {
+GL_HD bool te_operand(const TeLists& L, u32 i, int64_t src, int want, int operand) {
   if (te_class(L.nodes[src]) != want) {
     tt_report(L.defect, 8, i, operand);
     return false;
@@ -204,7 +198,7 @@ TT_HD bool te_operand(const TeLists& L, u32 i, int64_t src, int want, int operan
 }
 
 // a lane per body row: the node's operands (class, modulus, `is`), its cycles against the absorptions of p2, and its reads of its operands
-TT_HD void te_row_check(const TeLists& L, u32 r) {
+GL_HD void te_row_check(const TeLists& L, u32 r) {
   u32 idx;
   const u32 i = te_node_of(L, r, &idx);
   const mh_te_node x = L.nodes[i];
@@ -245,7 +239,7 @@ TT_HD void te_row_check(const TeLists& L, u32 r) {
 }
 
 // a lane per node, behind the counting: a truthy node is read once (the root never), a value node at least once
-TT_HD void te_read_check(const TeLists& L, u32 i) {
+GL_HD void te_read_check(const TeLists& L, u32 i) {
   const u32 reads = L.count[i];
   if (te_class(L.nodes[i]) == TE_CLASS_TRUTHY) {
     if (i == L.root) {
@@ -259,7 +253,7 @@ TT_HD void te_read_check(const TeLists& L, u32 i) {
 }
 
 // row r of the 39-column trace
-TT_HD void te_row(const TeLists& L, u64 n, u64* out, u64 r) {
+GL_HD void te_row(const TeLists& L, u64 n, u64* out, u64 r) {
   u64 row[TE_WIDTH];
   for (int k = 0; k < TE_WIDTH; k++) row[k] = 0;
   if (r < L.n_body) {

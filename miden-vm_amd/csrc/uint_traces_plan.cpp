@@ -7,25 +7,10 @@
 //   3 log_usm / log_add below the height needed   4 a store ptr that is 0 or not above the one before
 //   5 a gap to the next ptr >= 2^16               6 a bound_ptr that is not stored     7 a value above its bound's
 // The relations' own pointers and operands (kinds 8..14) are the witness pass's to judge.
-#include "../../include/midenhip.h"
+#include "ledger_plan.hpp"
 #include <vector>
 
 namespace {
-constexpr uint64_t UT_MAX_ROWS = (uint64_t)1 << 24;
-
-int ut_defect(mh_uint_traces_info* info, int section, int kind, uint64_t index) {
-  info->defect_section = section;
-  info->defect_kind = kind;
-  info->defect_index = index;
-  return MH_ERR_INVALID;
-}
-
-uint64_t ut_pow2(uint64_t v) {  // the least power of two >= max(1, v); v stays far below 2^63 here
-  uint64_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
 // the index of the row with pointer `ptr`, or n
 size_t ut_find(const mh_uint_row* rows, size_t n, uint32_t ptr) {
   size_t lo = 0, hi = n;
@@ -44,33 +29,32 @@ extern "C" int mh_uint_traces_plan(const mh_uint_row* rows, size_t n_store, cons
   info->n_store = n_store;
   info->n_mul = n_mul;
   info->n_add = n_add;
-  if (!rows && n_store) return ut_defect(info, 0, 1, 0);
-  if (!muls && n_mul) return ut_defect(info, 1, 1, 0);
-  if (!adds && n_add) return ut_defect(info, 2, 1, 0);
+  if (!rows && n_store) return plan_defect_in(info, 0, 1, 0);
+  if (!muls && n_mul) return plan_defect_in(info, 1, 1, 0);
+  if (!adds && n_add) return plan_defect_in(info, 2, 1, 0);
   // heights: a count above 2^24 cannot fit whatever the factor, and is not multiplied
-  if (n_store > UT_MAX_ROWS / 4) return ut_defect(info, 0, 2, n_store);
-  if (n_mul > UT_MAX_ROWS / 8) return ut_defect(info, 1, 2, n_mul);
-  if (n_add > UT_MAX_ROWS / 2) return ut_defect(info, 2, 2, n_add);
-  const uint64_t mul_rows = ut_pow2(8 * (uint64_t)(n_mul ? n_mul : 1));
-  uint64_t blocks = ut_pow2(n_store);
+  if (n_store > PLAN_MAX_ROWS / 4) return plan_defect_in(info, 0, 2, n_store);
+  if (n_mul > PLAN_MAX_ROWS / 8) return plan_defect_in(info, 1, 2, n_mul);
+  if (n_add > PLAN_MAX_ROWS / 2) return plan_defect_in(info, 2, 2, n_add);
+  const uint64_t mul_rows = pow2_at_least(8 * (uint64_t)n_mul, 8);
+  uint64_t blocks = pow2_at_least(n_store, 1);
   if (blocks < mul_rows / 4) blocks = mul_rows / 4;
   info->usm_rows_needed = 4 * blocks;
-  info->add_rows_needed = ut_pow2(2 * (uint64_t)(n_add ? n_add : 1));
-  if (log_usm > 24) return ut_defect(info, 0, 2, log_usm);
-  if (log_add > 24) return ut_defect(info, 2, 2, log_add);
-  info->usm_rows = log_usm >= 0 ? (uint64_t)1 << log_usm : info->usm_rows_needed;
-  info->add_rows = log_add >= 0 ? (uint64_t)1 << log_add : info->add_rows_needed;
+  info->add_rows_needed = pow2_at_least(2 * (uint64_t)n_add, 2);
+  if (log_usm > 24) return plan_defect_in(info, 0, 2, log_usm);
+  if (log_add > 24) return plan_defect_in(info, 2, 2, log_add);
+  const bool usm_fits = plan_height(log_usm, info->usm_rows_needed, &info->usm_rows), add_fits = plan_height(log_add, info->add_rows_needed, &info->add_rows);
   {  // padding blocks take last ptr + 1 + k: the last of them must stay a 32-bit pointer
     const uint64_t taken = info->usm_rows > info->usm_rows_needed ? info->usm_rows : info->usm_rows_needed;
     const uint64_t last = n_store ? rows[n_store - 1].ptr : 0;
-    if (last + (taken / 4 - n_store) > 0xffffffffull) return ut_defect(info, 0, 2, taken / 4 - n_store);
+    if (last + (taken / 4 - n_store) > 0xffffffffull) return plan_defect_in(info, 0, 2, taken / 4 - n_store);
   }
-  if (log_usm < -1 || info->usm_rows < info->usm_rows_needed) return ut_defect(info, 0, 3, info->usm_rows_needed);
-  if (log_add < -1 || info->add_rows < info->add_rows_needed) return ut_defect(info, 2, 3, info->add_rows_needed);
+  if (!usm_fits) return plan_defect_in(info, 0, 3, info->usm_rows_needed);
+  if (!add_fits) return plan_defect_in(info, 2, 3, info->add_rows_needed);
   for (size_t i = 0; i < n_store; i++)
-    if (rows[i].ptr == 0 || (i && rows[i].ptr <= rows[i - 1].ptr)) return ut_defect(info, 0, 4, i);
+    if (rows[i].ptr == 0 || (i && rows[i].ptr <= rows[i - 1].ptr)) return plan_defect_in(info, 0, 4, i);
   for (size_t i = 0; i + 1 < n_store; i++)
-    if (rows[i + 1].ptr - rows[i].ptr - 1 >= 0x10000u) return ut_defect(info, 0, 5, i);
+    if (rows[i + 1].ptr - rows[i].ptr - 1 >= 0x10000u) return plan_defect_in(info, 0, 5, i);
   std::vector<uint32_t> own;
   uint32_t* bi = bound_index;
   if (!bi) {
@@ -79,14 +63,14 @@ extern "C" int mh_uint_traces_plan(const mh_uint_row* rows, size_t n_store, cons
   }
   for (size_t i = 0; i < n_store; i++) {
     const size_t b = rows[i].bound_ptr == rows[i].ptr ? i : ut_find(rows, n_store, rows[i].bound_ptr);
-    if (b == n_store) return ut_defect(info, 0, 6, i);
+    if (b == n_store) return plan_defect_in(info, 0, 6, i);
     bi[i] = (uint32_t)b;
   }
   for (size_t i = 0; i < n_store; i++) {
     const uint32_t* v = rows[i].value;
     const uint32_t* b = rows[bi[i]].value;
     for (int j = 7; j >= 0; j--) {
-      if (v[j] > b[j]) return ut_defect(info, 0, 7, i);
+      if (v[j] > b[j]) return plan_defect_in(info, 0, 7, i);
       if (v[j] < b[j]) break;
     }
   }

@@ -1,11 +1,15 @@
 """CPU-only parts of the device-built UintStoreMul and UintAdd traces (include/midenhip.h mh_uint_traces_plan, mh_uint_traces_build): the
 planner's heights and bound indices against a restatement written here, every planner refusal by section, kind and index -- alone and
 with a higher kind behind it --, the empty lists, `uint_lists` of two sessions' ledgers against the reads the generators recorded, and
-the ABI across header, Rust declarations, Python layer and the built library."""
+the ABI across header, Rust declarations, Python layer and the built library; then the device stage's per-lane bodies
+(csrc/uint_traces_rows.cuh) run lane by lane on the host (tools/libuint_traces_cpu.so, built by __graft_entry__.build()) against the
+generators cell for cell and against the refusals tests/test_gpu_uint_traces.py expects of the device -- on the ledgers and defects that
+file gives the device (tests/uint_traces_cases.py)."""
 import ctypes as C
-import os, re
+import os, random, re
 import numpy as np
 import pytest
+import uint_traces_cases as UT
 from __graft_entry__ import load_package, ROOT
 
 pkg = load_package()
@@ -231,3 +235,103 @@ def test_abi_agrees_across_header_rust_python_and_library():
     assert "Not in scope" in sec
     for word in ("interning", "computing r", "sorting the store", "EC point store", "MSM", "transcript-eval", "device-resident", "sharded", "2^24"):
         assert word in sec[sec.index("Not in scope"):], word
+
+
+# ---- the per-lane bodies, lane by lane on the host ----
+WAVE, ROWS_BT = 64, 256   # a wave; the block of ut_self and of both row writers
+
+
+def witness_bt():
+    src = open(os.path.join(ROOT, "miden-vm_amd", "csrc", "uint_traces_rows.cuh")).read()
+    return int(re.search(r"UT_WITNESS_BT = (\d+)", src).group(1))
+
+
+def _vp(x):
+    return x.ctypes.data_as(C.c_void_p) if x.size else None
+
+
+@pytest.fixture(scope="module")
+def build():
+    """-> build(rows, muls, adds, log_usm, log_add) -> (rc, info, usm, add): the planner, the witness pass, then the row bodies on the host"""
+    so = os.path.join(ROOT, "tools", "libuint_traces_cpu.so")
+    assert os.path.exists(so), "tools/libuint_traces_cpu.so is missing: run __graft_entry__.build()"
+    cpu = C.CDLL(so)
+    cpu.uint_traces_cpu.argtypes = [C.c_void_p, C.c_size_t] * 3 + [C.c_int] * 2 + [C.c_void_p] * 2 + [C.POINTER(pkg.UintTracesInfo)]
+
+    def run(rows, muls, adds, log_usm=-1, log_add=-1):
+        try:
+            _, plan = pkg.uint_traces_plan(rows, muls, adds, log_usm, log_add, sort=False)
+        except pkg.MidenHipError as e:
+            return 1, e.info, None, None
+        usm, add = np.full((44, int(plan.usm_rows)), 0xdead, dtype=np.uint64), np.full((30, int(plan.add_rows)), 0xdead, dtype=np.uint64)
+        info = pkg.UintTracesInfo()
+        rc = cpu.uint_traces_cpu(_vp(rows), rows.size, _vp(muls), muls.size, _vp(adds), adds.size, log_usm, log_add, _vp(usm), _vp(add), C.byref(info))
+        return (rc, info, None, None) if rc else (0, info, usm.T, add.T)
+    return run
+
+
+def check(build, store, adds, muls, log_usm=-1, log_add=-1):
+    """host runner == generator, cell for cell, at the least heights or the given ones -> (usm, add, info)"""
+    exp_usm, exp_add = UT.generator(store, adds, muls, (1 << log_usm) if log_usm >= 0 else 0, (1 << log_add) if log_add >= 0 else 0)
+    rows, m, a = PT.uint_lists(store, adds, muls)
+    rc, info, usm, add = build(rows, m, a, log_usm, log_add)
+    assert rc == 0, info
+    UT.same(usm, exp_usm)
+    UT.same(add, exp_add)
+    assert (info.n_store, info.n_mul, info.n_add, info.usm_rows, info.add_rows, info.defect_kind) == (rows.size, m.size, a.size, usm.shape[0], add.shape[0], 0)
+    return usm, add, info
+
+
+@pytest.mark.parametrize("bound", UT.EDGE_BOUNDS, ids=[f"{b:#x}"[:12] for b in UT.EDGE_BOUNDS])
+def test_edge_moduli_one_store_and_seven_relations(build, bound):
+    store, adds, muls = UT.edge_ledgers(bound)
+    assert len(muls.ops) == (7 if bound else 6)
+    usm, add, _ = check(build, store, adds, muls)
+    assert (usm.shape[0], add.shape[0]) == (64, 8)
+
+
+def _around(x):
+    return (x - 1, x, x + 1)
+
+
+def boundary_counts():
+    """(n_mul, n_add, n_store or None) with one count below, at and above a wave and a block of each stage: the witness pass has a lane per
+    relation, ut_self one per stored value; the row writers have eight rows per multiply relation and two per addition"""
+    w = witness_bt()
+    cases = [(n, n, None) for n in sorted(set(_around(WAVE) + _around(w)))]
+    cases += [(m, a, None) for m, a in zip(_around(WAVE // 8) + _around(ROWS_BT // 8), _around(WAVE // 2) + _around(ROWS_BT // 2))]
+    cases += [(3, 3, s) for s in _around(WAVE) + _around(ROWS_BT)]
+    return cases
+
+
+@pytest.mark.parametrize("n_mul, n_add, n_store", boundary_counts(), ids=lambda v: str(v))
+def test_wave_and_block_boundaries_of_each_stage(build, n_mul, n_add, n_store):
+    rng = random.Random(1000 + 7 * n_mul + n_add + (n_store or 0))
+    bound = rng.getrandbits(rng.choice([64, 200, 256])) | 1 << 63
+    store, adds, muls = UT.random_ledgers(rng, bound, n_mul, n_add)
+    if n_store is not None:
+        fp = min(store.rows)
+        assert len(store.rows) <= n_store
+        while len(store.rows) < n_store:
+            store.intern(rng.randrange(bound + 1), fp)
+    usm, add, info = check(build, store, adds, muls)
+    assert (info.n_mul, info.n_add) == (n_mul, n_add) and (n_store is None or info.n_store == n_store)
+    assert usm.shape[0] == max(1 << (8 * n_mul - 1).bit_length(), 4 << (len(store.rows) - 1).bit_length()) and add.shape[0] == 1 << (2 * n_add - 1).bit_length()
+
+
+def test_forced_heights_above_the_need(build):
+    rng = random.Random(5)
+    store, adds, muls = UT.random_ledgers(rng, UT.K1, 20, 9)
+    usm, add, info = check(build, store, adds, muls, log_usm=11, log_add=7)
+    assert info.usm_rows_needed < 2048 and (info.add_rows_needed, usm.shape[0], add.shape[0]) == (32, 2048, 128)
+
+
+def test_witness_pass_refuses_every_device_kind(build):
+    cases = UT.device_defects()
+    assert {c[4] for c in cases} == set(range(8, 15))
+    for store, adds, muls, section, kind, index, operand, _ in cases:
+        rows, m, a = PT.uint_lists(store, adds, muls)
+        rc, info, usm, add = build(rows, m, a)
+        assert rc != 0 and usm is None, "a defective ledger must be refused"
+        assert (info.defect_section, info.defect_kind, info.defect_index, info.defect_operand) == (section, kind, index, operand), info
+        assert (info.n_store, info.n_mul, info.n_add, info.usm_rows_needed, info.add_rows_needed) == (rows.size, 8, 8, 256, 16)

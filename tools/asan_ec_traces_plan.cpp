@@ -5,6 +5,7 @@
 // every field any 32-bit value, n_rows that sum to anything, counts above the row limit with no list behind them, every log from -3 to
 // 40 -- in heap blocks of exactly the stated sizes, so that a read past a list is an error of the sanitizer.  Exit code 0 and "clean"
 // only if all of that holds.
+#include "asan_common.hpp"
 #include "../include/midenhip.h"
 #include <cstdio>
 #include <cstdlib>
@@ -13,24 +14,6 @@
 #include <vector>
 
 static std::mt19937_64 rng(4242);
-static int failures = 0;
-#define EXPECT(cond, what)                                       \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      fprintf(stderr, "FAILED: %s (line %d)\n", what, __LINE__); \
-      failures++;                                                \
-    }                                                            \
-  } while (0)
-
-template <class T>
-struct Exact {  // a heap copy of exactly the stated size
-  T* p;
-  explicit Exact(const std::vector<T>& v) : p(v.empty() ? nullptr : (T*)malloc(v.size() * sizeof(T))) {
-    if (p) memcpy(p, v.data(), v.size() * sizeof(T));
-  }
-  ~Exact() { free(p); }
-};
-
 struct Lists {
   std::vector<mh_ec_group> groups;
   std::vector<mh_ec_point> points;
@@ -54,12 +37,6 @@ static int plan(const Lists& l, const int (&logs)[4], std::vector<uint32_t>* row
     *row_start = rs;
   }
   return rc;
-}
-
-static uint64_t pow2(uint64_t v, uint64_t least) {
-  uint64_t p = least;
-  while (p < v) p <<= 1;
-  return p;
 }
 
 static const int LEAST[4] = {-1, -1, -1, -1};
@@ -218,10 +195,5 @@ int main() {
     if (rc != MH_OK)
       for (uint32_t v : rs) EXPECT(v == 0xdeadbeefu, "a refusal writes no first row");
   }
-  if (failures) {
-    fprintf(stderr, "%d failures\n", failures);
-    return 1;
-  }
-  printf("asan_ec_traces_plan: clean\n");
-  return 0;
+  return verdict("asan_ec_traces_plan");
 }

@@ -5,6 +5,8 @@
 // mh_lmcs_verify  (1) the openings, which must be accepted,  (2) every damage class of tests/test_lmcs_verify.py, which must be
 // refused,  (3) random lengths, counts, heights, widths, alignments and indices around them, which must neither be accepted when
 // they differ from the opening nor touch memory they do not own.  Exit code 0 and "clean" only if all of that holds.
+#include "asan_common.hpp"
+#include <string>
 #include "../include/midenhip.h"
 #include "../miden-vm_amd/csrc/gl.cuh"
 #include "../miden-vm_amd/csrc/lmcs_host.hpp"
@@ -18,15 +20,6 @@
 
 static std::mt19937_64 rng(12345);
 static u64 felt() { return rng() % GL_P; }
-static int failures = 0;
-#define EXPECT(cond, what)                                  \
-  do {                                                      \
-    if (!(cond)) {                                          \
-      fprintf(stderr, "FAILED: %s (line %d)\n", what, __LINE__); \
-      failures++;                                           \
-    }                                                       \
-  } while (0)
-
 struct Made {
   int lmcs, salt, depth;
   size_t alignment;
@@ -201,10 +194,5 @@ int main() {
     }
     EXPECT(below == 1 || depth == 0, "the plan ends in one node");
   }
-  if (failures) {
-    fprintf(stderr, "%d failures in %zu calls\n", failures, n_calls);
-    return 1;
-  }
-  printf("clean: %zu calls of mh_lmcs_verify, no failure\n", n_calls);
-  return 0;
+  return verdict((std::to_string(n_calls) + " calls of mh_lmcs_verify").c_str());
 }

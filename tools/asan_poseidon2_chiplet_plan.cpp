@@ -4,6 +4,7 @@
 // ledgers with one defect of every kind, which must be refused with that kind and index, and  (3) hostile lists: counts that wrap,
 // n_cycles far from the sum, references of any 64-bit value -- in heap blocks of exactly the stated sizes, so that a read past a list
 // is an error of the sanitizer.  Exit code 0 and "clean" only if all of that holds.
+#include "asan_common.hpp"
 #include "../include/midenhip.h"
 #include <cstdio>
 #include <cstdlib>
@@ -12,25 +13,7 @@
 #include <vector>
 
 static std::mt19937_64 rng(4242);
-static int failures = 0;
-#define EXPECT(cond, what)                                       \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      fprintf(stderr, "FAILED: %s (line %d)\n", what, __LINE__); \
-      failures++;                                                \
-    }                                                            \
-  } while (0)
-
 // heap copies of exactly the stated sizes
-template <class T>
-struct Exact {
-  T* p;
-  explicit Exact(const std::vector<T>& v) : p(v.empty() ? nullptr : (T*)malloc(v.size() * sizeof(T))) {
-    if (p) memcpy(p, v.data(), v.size() * sizeof(T));
-  }
-  ~Exact() { free(p); }
-};
-
 static int plan(const std::vector<mh_p2c_absorption>& abs, const std::vector<int64_t>* refs, size_t n_cycles, std::vector<uint64_t>& start,
                 std::vector<uint32_t>& level, mh_p2c_info& info) {
   Exact<mh_p2c_absorption> a(abs);
@@ -127,10 +110,5 @@ int main() {
     EXPECT(mh_poseidon2_chiplet_plan(nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr) == MH_ERR_INVALID, "no info");
     EXPECT(mh_poseidon2_chiplet_plan(nullptr, 0, nullptr, 0, nullptr, nullptr, &info) == MH_OK && info.rows_needed == 16 && info.n_levels == 0, "empty");
   }
-  if (failures) {
-    fprintf(stderr, "%d failure(s)\n", failures);
-    return 1;
-  }
-  printf("clean\n");
-  return 0;
+  return verdict("asan_poseidon2_chiplet_plan");
 }

@@ -6,6 +6,7 @@
 // any 64-bit value (or one near the limits the planners compare with), kinds and ops anything, spans that wrap, every log from -3 to 40 --
 // in heap blocks of exactly the stated sizes, so that a read past a list is an error of the sanitizer.  Neither planner reads through
 // `bytes`, `digests` or `limbs`: those are dangling non-null pointers here.  Exit code 0 and "clean" only if all of that holds.
+#include "asan_common.hpp"
 #include "../include/midenhip.h"
 #include <cstdio>
 #include <cstdlib>
@@ -14,32 +15,8 @@
 #include <vector>
 
 static std::mt19937_64 rng(777);
-static int failures = 0;
-#define EXPECT(cond, what)                                       \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      fprintf(stderr, "FAILED: %s (line %d)\n", what, __LINE__); \
-      failures++;                                                \
-    }                                                            \
-  } while (0)
-
-template <class T>
-struct Exact {  // a heap copy of exactly the stated size
-  T* p;
-  explicit Exact(const std::vector<T>& v) : p(v.empty() ? nullptr : (T*)malloc(v.size() * sizeof(T))) {
-    if (p) memcpy(p, v.data(), v.size() * sizeof(T));
-  }
-  ~Exact() { free(p); }
-};
-
 static const uint8_t* const DANGLING8 = (const uint8_t*)(uintptr_t)0x10;    // never read through
 static const uint32_t* const DANGLING32 = (const uint32_t*)(uintptr_t)0x10;
-
-static uint64_t pow2(uint64_t v) {
-  uint64_t p = 2;
-  while (p < v) p <<= 1;
-  return p;
-}
 
 // ---------------------------------------------------------------- ChunkNode ----------------------------------------------------------------
 struct Cn {
@@ -84,7 +61,7 @@ static void cn_tests() {
     for (const mh_kn_record& r : l.rec) total += chunks_of(r.len);
     mh_chunk_node_info info;
     EXPECT(cn_plan(l, -1, info) == MH_OK && info.defect_kind == 0, "a well-formed list is accepted");
-    EXPECT(info.rows == pow2(total > n ? total : n) && info.rows_needed == info.rows && info.n_chunks == total && info.n_records == n, "heights");
+    EXPECT(info.rows == pow2(total > n ? total : n, 2) && info.rows_needed == info.rows && info.n_chunks == total && info.n_records == n, "heights");
     EXPECT(cn_plan(l, 24, info) == MH_OK && info.rows == (uint64_t)1 << 24, "a larger log pads");
     if (n == 0) continue;
     const size_t i = rng() % n;
@@ -242,7 +219,7 @@ static void te_tests() {
       else at += l.nodes[i].kind == 8 ? (uint64_t)l.nodes[i].rhs : 1;
     }
     const uint64_t active = at + (zeros ? 1 : 0);
-    EXPECT(starts_ok && info.active_rows == active && info.n_zero == zeros && info.rows == pow2(active) && info.rows == info.rows_needed, "rows");
+    EXPECT(starts_ok && info.active_rows == active && info.n_zero == zeros && info.rows == pow2(active, 2) && info.rows == info.rows_needed, "rows");
     EXPECT(te_plan(l, -1, nullptr, info) == MH_OK, "no row_start asked for");
     Te d = l;
     const size_t i = rng() % n;
@@ -366,10 +343,5 @@ static void te_tests() {
 int main() {
   cn_tests();
   te_tests();
-  if (failures) {
-    fprintf(stderr, "%d check(s) failed\n", failures);
-    return 1;
-  }
-  printf("asan_transcript_traces_plan: clean\n");
-  return 0;
+  return verdict("asan_transcript_traces_plan");
 }

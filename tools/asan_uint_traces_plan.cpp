@@ -5,6 +5,7 @@
 // 32-bit value in any order, bounds that point anywhere, counts above the row limit with no list behind them, every log from -3 to 40 --
 // in heap blocks of exactly the stated sizes, so that a read past a list is an error of the sanitizer.  Exit code 0 and "clean" only if
 // all of that holds.
+#include "asan_common.hpp"
 #include "../include/midenhip.h"
 #include <algorithm>
 #include <cstdio>
@@ -14,24 +15,6 @@
 #include <vector>
 
 static std::mt19937_64 rng(777);
-static int failures = 0;
-#define EXPECT(cond, what)                                       \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      fprintf(stderr, "FAILED: %s (line %d)\n", what, __LINE__); \
-      failures++;                                                \
-    }                                                            \
-  } while (0)
-
-template <class T>
-struct Exact {  // a heap copy of exactly the stated size
-  T* p;
-  explicit Exact(const std::vector<T>& v) : p(v.empty() ? nullptr : (T*)malloc(v.size() * sizeof(T))) {
-    if (p) memcpy(p, v.data(), v.size() * sizeof(T));
-  }
-  ~Exact() { free(p); }
-};
-
 static int plan(const std::vector<mh_uint_row>& rows, size_t n_mul, size_t n_add, int log_usm, int log_add, std::vector<uint32_t>* bound_index,
                 mh_uint_traces_info& info) {
   Exact<mh_uint_row> r(rows);
@@ -47,12 +30,6 @@ static int plan(const std::vector<mh_uint_row>& rows, size_t n_mul, size_t n_add
     *bound_index = bi;
   }
   return rc;
-}
-
-static uint64_t pow2(uint64_t v) {
-  uint64_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
 }
 
 // a well-formed store: a few modulus rows (their own bound), values under them, ascending pointers with gaps below 2^16
@@ -193,10 +170,5 @@ int main() {
     EXPECT(mh_uint_traces_plan(&one, 1, nullptr, 0, nullptr, 0, -1, -1, nullptr, &info) == MH_OK, "the last padding pointer may be 2^32 - 1");
     EXPECT(mh_uint_traces_plan(&one, 1, nullptr, 0, nullptr, 0, 4, -1, nullptr, &info) == MH_ERR_INVALID && info.defect_kind == 2, "kind 2: padding pointers of a larger height");
   }
-  if (failures) {
-    fprintf(stderr, "%d failures\n", failures);
-    return 1;
-  }
-  printf("asan_uint_traces_plan: clean\n");
-  return 0;
+  return verdict("asan_uint_traces_plan");
 }

@@ -20,11 +20,8 @@ extern "C" int ec_traces_cpu(const mh_ec_group* groups, size_t n_groups, const m
   for (u32 i = 0; i < L.n_add; i++) ec_add_check(L, i);
   for (u32 i = 0; i < L.n_exprs; i++) ec_expr_check(L, i);
   for (u32 i = 0; i < L.n_terms; i++) ec_term_check(L, i);
-  if (defect != ~0ull) {
-    info->defect_kind = (int32_t)(defect >> 56);
-    info->defect_section = (int32_t)((defect >> 54) & 3);
-    info->defect_index = (defect >> 8) & 0xffffffffull;
-    info->defect_operand = (int32_t)(defect & 0xff);
+  if (const LedgerDefect d = ledger_unpack(defect); d.kind) {
+    info->defect_kind = d.kind; info->defect_section = d.section; info->defect_index = d.index; info->defect_operand = d.operand;
     return MH_ERR_INVALID;
   }
   for (u64 t = 0; t < info->groups_rows; t++) ec_groups_row(L, info->groups_rows, groups_out, t);

@@ -9,9 +9,8 @@
 namespace {
 template <class Info>
 int unpack(unsigned long long defect, Info* info) {
-  info->defect_kind = (int32_t)(defect >> 56);
-  info->defect_index = (defect >> 8) & 0xffffffffull;
-  info->defect_operand = (int32_t)(defect & 0xff);
+  const LedgerDefect d = ledger_unpack(defect);
+  info->defect_kind = d.kind; info->defect_index = d.index; info->defect_operand = d.operand;
   return MH_ERR_INVALID;
 }
 }  // namespace
